@@ -16,9 +16,16 @@ runs whole on HIP stream k mod 2 with its own buffers, so one batch's kernels
 fill the SIMDs the other's leave idle; every timed step is still a full K1 + K3
 + K2 of its batch, and both batches' results are checked after the timed steps.
 The launches alone (one batch at a time, after the timed region) are reported
-as kernel_ms_isolated / roofline_isolated.
+as kernel_ms_isolated / roofline_isolated (--full).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps, checks the timed steps' own
+results on the device (statuses, round trip), writes them (--dump-outputs DIR)
+and prints one JSON line.  Everything that takes a run of its own is behind
+--full: the launches alone, the device-to-device copy peak, the host-memory
+(PCIe-inclusive) rates, the CPU baseline with its byte comparison against the
+oracle, and for N>1 the timed payload gather.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N>1: under python -m torch.distributed.run --nproc-per-node N bench.py --gpus N, or
         bench.py --gpus N alone, which starts that launcher as a child process itself)
 """
@@ -81,6 +88,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="auto", choices=["auto"] + sorted(WORKLOADS),
                     help="auto: c1 on one GPU (BASELINE configs[1]), c3 sharded over N>1 GPUs (configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own: the launches alone (kernel_ms_isolated), "
+                         "the copy peak, the host-memory rates (e2e), the CPU baseline and oracle comparison, the N>1 "
+                         "payload gather (each can be switched off again with its --no-... option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64 / float32; the two byte buffers as a fixed, seeded sample of positions)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample duration")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-memory (PCIe-inclusive) measurement")
@@ -428,6 +442,38 @@ def checksum(x, chunk: int = 1 << 26) -> int:
     return int(acc)
 
 
+DUMP_SAMPLE = 4 << 20  # positions kept of each byte buffer (float32: 16 MiB a file, under 64 MB in all)
+
+
+def dump_outputs(path, b, count, total):
+    """--dump-outputs: what the last timed step handed back (buffer set `b`), one
+    DIR/<name>.npy each.  The per-stream arrays whole, as float64 (exact: all are
+    below 2^53): K1's compressed sizes and statuses, K3's packed offsets, K2's
+    output sizes and statuses.  The two byte buffers, K3's packed payload
+    (`packed`, packed_offsets[-1] bytes) and K2's decoded output (`out`, `total`
+    bytes), as float32 at DUMP_SAMPLE sorted positions drawn with a fixed seed
+    (the whole buffer when it is no longer than that)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    cbk = b["cb"]
+    comp_bytes = int(b["poff"][-1])
+    arrays = {
+        "compressed_sizes": cbk.sizes[:count], "compress_status": cbk.status[:count], "packed_offsets": b["poff"][: count + 1],
+        "out_sizes": b["osz"][:count], "decompress_status": b["ost"][:count],
+    }
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), x.cpu().numpy().astype(np.float64))
+    for k, (name, x, n) in enumerate((("packed", b["packed"], comp_bytes), ("out", b["out"], total))):
+        if n > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(20240 + k).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+            x = x[torch.from_numpy(pos).to(x.device)]
+        else:
+            x = x[:n]
+        np.save(os.path.join(path, name + ".npy"), x.cpu().numpy().astype(np.float32))
+
+
 def gather_check(ez, ezd, R, packed, goff, count_all, first_all, data, size, dev, reps=3):
     """The optional payload gather of the sharded path, timed
     separately: every rank's packed shard to rank 0 at its global offset.  Then
@@ -635,11 +681,13 @@ def main():
             base = int(goff[0][first_all[rank]])
             assert torch.equal(goff[0][first_all[rank] : first_all[rank + 1] + 1] - base, poff), "global offsets"
     comp_bytes = int(poff[-1])
+    if args.dump_outputs and rank == 0 and args.steps:  # (N > 1: rank 0's shard)
+        dump_outputs(args.dump_outputs, sets[(args.steps - 1) % inflight], count, total)
     # with batches in flight each launch shares the chip with the other batches' kernels, so its event
     # time is longer than the launch alone; the launches alone, after the timed region (untimed): one
-    # stream, steps back to back
+    # stream, steps back to back (--full)
     iso = None
-    if inflight > 1:
+    if args.full and inflight > 1:
         ievs = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(3)]
         torch.cuda.synchronize()
         for e in ievs:
@@ -648,7 +696,7 @@ def main():
         iso = [sum(e[a].elapsed_time(e[a + 1]) for e in ievs) / len(ievs) for a in (0, 1, 3)]
     elapsed, k1, k2, k3, xch = ezd.reduce_max([elapsed, k1, k2, k3, xch], R, dev)  # the job ends with its slowest rank
     (comp_all,) = ezd.reduce_sum([comp_bytes], R, dev)
-    peak_meas = copy_peak(dev) if rank == 0 else None  # after the timed region: the second denominator
+    peak_meas = copy_peak(dev) if args.full and rank == 0 else None  # after the timed region: the second denominator
 
     ms = elapsed / args.steps * 1e3
     gib_step = count_all * size / 2**30
@@ -713,8 +761,9 @@ def main():
         "kernel_ms_note": ("event time of each launch in the timed steps, on its own stream; with batches in flight a "
                            "launch shares the chip with the other batch's kernels, so it is longer than the launch alone "
                            "(kernel_ms_isolated, roofline_isolated: the same launches one batch at a time, after the "
-                           "timed region)" if inflight > 1 else "event time of each launch in the timed steps"),
+                           "timed region, with --full)" if inflight > 1 else "event time of each launch in the timed steps"),
         "cpu_baseline": None,
+        "full": args.full,
     }
     if iso is not None:
         k1i, k3i, k2i = ezd.reduce_max(iso, R, dev)
@@ -726,14 +775,14 @@ def main():
                                     "frac": alg / (domi / 1e3) / 1e9 / HBM_PEAK_GBS}
     if sharded:
         res["kernel_ms"]["size_exchange"] = xch
-        if not args.no_gather:
+        if args.full and not args.no_gather:
             res["gather"] = gather_check(ez, ezd, R, packed, goff[0], count_all, first_all, data, size, dev)
-    if not args.no_e2e and world == 1:
+    if args.full and not args.no_e2e and world == 1:
         res["e2e"] = e2e(ez, data, off, cb, packed, poff, ws, dws, out, osz, ost, block, htable, size, total, comp_bytes)
         if count >= 2 * args.e2e_chunks:
             res["e2e"]["pipelined"] = e2e_pipelined(ez, data, off, offs, cb, packed, poff, dws, out, osz, ost, block, htable,
                                                     size, total, comp_bytes, chunks=args.e2e_chunks)
-    if rank == 0 and not args.no_cpu:  # N > 1: rank 0's shard (the other ranks' streams are alike)
+    if args.full and rank == 0 and not args.no_cpu:  # N > 1: rank 0's shard (the other ranks' streams are alike)
         cb_res, checked = cpu_baseline(host, offs, block, htable, args.cpu_seconds, packed.cpu().numpy(), poff.cpu().numpy())
         res["cpu_baseline"] = cb_res
         res["parity"] = {"streams_byte_compared_with_oracle": checked, "streams": count,

@@ -206,18 +206,55 @@ def test_reader_refill_offers_go_capacity(cuda):
 
 def test_bench_batches_in_flight(cuda):
     """bench.py's default schedule (two batches in flight on two HIP streams, each with its own
-    buffers) completes every step and checks both batches' statuses and round trips itself; its
-    line carries the launches-alone times beside the timed ones."""
+    buffers) completes every step and checks both batches' statuses and round trips itself; with
+    --full its line carries the launches-alone times beside the timed ones."""
     import json
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu", "--no-e2e", "--steps", "3", "--warmup", "2",
-                        "--streams", "8192"], capture_output=True, text=True, timeout=240, cwd=root)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu", "--no-e2e", "--steps", "3",
+                        "--warmup", "2", "--streams", "8192"], capture_output=True, text=True, timeout=240, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
     assert d["config"]["batches_in_flight"] == 2 and d["value"] > 0
     assert set(d["kernel_ms_isolated"]) == {"k1_compress", "k3_pack", "k2_decompress"}
     assert 0 < d["roofline_isolated"]["frac"] < 1
+
+
+def test_bench_plain_run_dumps_outputs(cuda, tmp_path):
+    """A plain bench.py run (no --full) times the steps and prints the headline keys without the
+    measurements that take runs of their own; --dump-outputs writes the last timed step's results:
+    the per-stream arrays whole, the byte buffers at seeded positions (8,192 x 4 KiB = 32 MiB is past
+    the sample size, so the sampled path runs), and the decoded sample equals the input's bytes."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from eazy_amd import synth
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    S, n = 8192, 4096
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--streams", str(S), "--dump-outputs", str(tmp_path / "o")], capture_output=True, text=True,
+                       timeout=240, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "GiB/s" and d["dtype"] == "u8"
+    assert abs(d["value"] - S * n / 2**30 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
+    for k in ("kernel_ms_isolated", "roofline_isolated", "e2e", "parity", "gather"):
+        assert k not in d
+    assert d["cpu_baseline"] is None and d["roofline"]["achievable_peak"] is None and d["full"] is False
+    a = {f[:-4]: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert set(a) == {"compressed_sizes", "compress_status", "packed_offsets", "out_sizes", "decompress_status", "packed", "out"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000
+    assert not a["compress_status"].any() and not a["decompress_status"].any()
+    assert np.array_equal(a["out_sizes"], np.full(S, n)) and a["packed_offsets"].shape == (S + 1,)
+    assert np.array_equal(np.diff(a["packed_offsets"]), a["compressed_sizes"])
+    assert a["packed"].shape == (bench.DUMP_SAMPLE,) and a["out"].shape == (bench.DUMP_SAMPLE,)
+    pos = np.sort(np.random.default_rng(20241).integers(0, S * n, bench.DUMP_SAMPLE, dtype=np.int64))
+    assert np.array_equal(a["out"], synth.logs(1000, S * n)[pos].astype(np.float32))

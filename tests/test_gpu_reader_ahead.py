@@ -142,11 +142,10 @@ def test_incompressible_and_zero_runs(cuda):
 
 def test_cpp_mirror_reader_ahead(cuda):
     """The C++ mirror's NewReader over the same handle path (eazy_test --reader-ahead)."""
-    import os
     import subprocess
 
-    exe = os.path.join(os.path.dirname(__file__), "cpp", "eazy_test")
-    if not os.path.exists(exe):
-        pytest.skip("tests/cpp/eazy_test not built")
+    from test_cpp import _build
+
+    exe = _build()  # (make: a no-op when tests/cpp/eazy_test is up to date)
     p = subprocess.run([exe, "--reader-ahead"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]

@@ -21,7 +21,7 @@ for W in ${WLS:-c1}; do
   done
   python3 tools/traffic.py $O/$W $O/traffic_$W.json $W ${SHAPE[$W]} > $O/$W/traffic.log 2>&1 || { echo "$W traffic failed"; cat $O/$W/traffic.log; exit 1; }
   E=--no-e2e; [ "$W" = c1 ] && E=""
-  timeout -k 10 600 python3 bench.py --traffic-json $O/traffic_$W.json --workload $W --steps ${STEPS:-10} $E > $O/$W.json 2> $O/$W.err
+  timeout -k 10 600 python3 bench.py --full --traffic-json $O/traffic_$W.json --workload $W --steps ${STEPS:-10} $E > $O/$W.json 2> $O/$W.err
   rc=$?; echo "$W bench rc=$rc $(python3 -c "import json;d=json.load(open('$O/$W.json'));c=d.get('cpu_baseline') or {};r=d['roofline'];print(round(d['value'],2), {k:round(v,3) for k,v in d['kernel_ms'].items()}, 'frac', round(r['frac'],4), 'traffic', r['traffic'], 'cpu', c.get('value'), c.get('single_thread',{}).get('value'))" 2>&1 | tail -1)"
   [ $rc -eq 0 ] || { tail -5 $O/$W.err; exit $rc; }
 done

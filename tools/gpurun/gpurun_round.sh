@@ -22,6 +22,6 @@ for C in FETCH_SIZE WRITE_SIZE; do
   rc=$?; echo "pmc $C rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 python3 tools/traffic.py $O $O/traffic_$WL.json $WL $STREAMS $SB > $O/traffic.log 2>&1
-timeout -k 10 600 python3 bench.py --traffic-json $O/traffic_$WL.json $ARGS > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python3 bench.py --full --traffic-json $O/traffic_$WL.json $ARGS > $O/bench.json 2> $O/bench.err
 rc=$?; echo "bench rc=$rc"; cat $O/bench.json
 exit $rc
