@@ -170,7 +170,8 @@ def select_compress_kernel(kind: str = "") -> None:
 
 def select_decompress_kernel(kind: str = "") -> None:
     """Force the first K2 kernel of later batch decodes ('r' ring, 't' token-parallel wave per
-    stream, 'w' wave per stream; '' = automatic).  Tests and A/B measurement only."""
+    stream, 'w' wave per stream, 'j' the chip-wide K2j for batches of at most 1,024 streams;
+    '' = automatic).  Tests and A/B measurement only."""
     _check(_lib().ez_select_decompress_kernel(ord(kind) if kind else 0))
 
 
@@ -780,7 +781,9 @@ def decompress_batch(comp, comp_off, out_off, block_size_limit: int = 0, out=Non
     the fast decoders (every stream on the exact decoder).  max_len (the largest
     slot), in_bytes = comp_off[-1] - comp_off[0] and out_bytes = out_off[-1] -
     out_off[0] are optional host hints: with them the call never waits for the
-    stream to pick its decoder."""
+    stream to pick its decoder.  in_bytes and out_bytes count only as a pair (one
+    alone is taken as unknown), and a wrong value costs speed, never memory
+    safety: a batch larger than its hints goes to the exact decoder."""
     import torch
 
     _need_cuda(comp, comp_off, out_off)

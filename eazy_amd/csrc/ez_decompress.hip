@@ -347,8 +347,10 @@ hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {
     // batches of more streams, whose chains K2t runs side by side (1,024 x 1 MiB: 12.9 / 58.8 ms).
     // K2j's time follows the batch's output, K2t's the longest stream's (256 x 1 MiB logs: K2t's
     // chain ~12.8 ms against K2j 15.6): K2j only while the output is at most 200 slots' worth.
-    // The extents are the caller's hints (ez_batch.in_bytes / out_bytes); without them, four offsets
-    // read back (which waits for the stream).
+    // The extents are the caller's hints (ez_batch.in_bytes / out_bytes, both or neither: one alone
+    // counts as unknown); without them, four offsets read back (which waits for the stream).  Wrong
+    // hints pick the slower route at worst: K2j checks them on the device before it sizes anything
+    // by the real offsets (kj_init) and hands an under-stated batch to the exact decoder.
     if (v == 't' && !a.force && sel == 0 && a.count <= 256 && a.max_out >= ((uint64_t)1 << 20)) {
         uint64_t nin = 0, nout = 0;
         if ((e = batch_extents(a, st, &nin, &nout)) != hipSuccess) return e;

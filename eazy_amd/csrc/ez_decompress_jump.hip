@@ -44,6 +44,10 @@
 //
 // Streams K2j cannot take as a whole (an error, a form k2_scan hands over, a MetaReset after output,
 // a slot too small) go to the exact decoder (ez_decompress.hip), which recomputes them from the start.
+//
+// Extent hints (ez_batch.in_bytes / out_bytes): the workspace is sized from them, so kj_init checks
+// them against the real offsets; a batch larger than its hints goes to the exact decoder as a whole
+// (kj_guarded).  Over-stated hints only make the workspace larger; one hint alone counts as none.
 #include <hip/hip_runtime.h>
 
 #include "ez_bytes.h"
@@ -97,9 +101,18 @@ struct JWork {
     JTok *ltok;         // kj_tok's records, chunk-local (kJRec per chunk, dst from the chunk's output start)
     uint32_t *cmaxd;    // the longest copy distance of a chunk
     uint32_t *ptr;
-    uint32_t *pass;     // [kJPasses]: the pass changed something; [kJPasses]: token records allocated
+    uint32_t *pass;     // [kJPasses]: the pass changed something; [kJPasses]: the guard (kj_init); then token records allocated
     int32_t jc;         // compressed bytes per chunk (jchunk)
+    // the input and output extents the workspace was sized from (the caller's hints, or read back):
+    // kj_init checks the real offsets against them
+    uint64_t in_ext, out_ext;
 };
+
+// The guard: the batch's real extents exceed the ones its workspace was sized from (an under-stated
+// ez_batch.in_bytes / out_bytes).  kj_init sets it; every later kernel but kj_final returns at once,
+// so nothing indexes the workspace by the real offsets, and kj_final queues every stream for the
+// exact decoder.
+__device__ __forceinline__ bool kj_guarded(const JWork &W) { return W.pass[kJPasses] != 0; }
 
 // Chunks of 256 bytes for batches of at most 96 KiB of input (a Reader's refill of ~64 KiB: four
 // times the lanes, each walk a quarter as long -- one wave of 1 KiB chunks was the refill's critical
@@ -188,44 +201,26 @@ __device__ __forceinline__ int32_t jadv_s(const JStage &S, uint64_t b0, int32_t 
     return r == kParseHandOver ? -1 : t.adv;
 }
 
-// The input bytes the token (or padding run, or meta) at the 16 bytes h takes, for the speculative
-// walks (kj_spec, kj_verify, kj_fix): the same advance as k2_scan for every form it accepts, from 32-bit
-// arithmetic on the header's first 8 bytes and no checks (a form k2_scan hands over advances by some
-// amount >= 1 here; kj_tok's full parse of the true chain then hands the stream over)
-__device__ __forceinline__ int32_t jadv_fast(V16 h) {
-    const uint32_t w0 = (uint32_t)h.lo, w1 = (uint32_t)(h.lo >> 32);
-    const uint32_t t0 = w0 & 0xff, l7 = t0 & 0x7f;
-    if (t0 == 0) return h.lo ? (int32_t)(__builtin_ctzll(h.lo) >> 3) : (h.hi ? 8 + (int32_t)(__builtin_ctzll(h.hi) >> 3) : 16);
-    if (t0 == 0x80) {
-        const uint32_t ml = (w0 >> 8) & 7;
-        return 2 + (ml == 7 ? 0 : (1 << ml));
-    }
-    const uint32_t ln = l7 >= 124 ? 1u << (l7 - 124 < 2 ? l7 - 124 : 2) : 0u;  // extra length bytes
-    const uint32_t j = 1 + ln;
-    if (!(t0 & 0x80)) {  // literal: the tag, then L bytes
-        const uint32_t lx = __builtin_amdgcn_alignbyte(w1, w0, 1);  // bytes 1..4
-        const uint32_t lmask = ln == 4 ? 0x3fffffffu : (1u << (8 * ln)) - 1;
-        const uint32_t L = l7 >= 124 ? 124u + (l7 >= 125 ? 256u : 0u) + (l7 >= 126 ? 65536u : 0u) + (lx & lmask) : l7;
-        const uint32_t adv = j + L;
-        return adv > 0x7fffffffu ? 0x7fffffff : (int32_t)adv;
-    }
-    // copy: the tag, the long prefix (0xff) if any, the offset byte and its 1, 2 or 4 extra bytes
-    const uint32_t bj = (uint32_t)(h.lo >> (8 * j)) & 0xff;  // (j <= 5)
-    const uint32_t jo = j + (bj == 0xff ? 1u : 0u);
-    const uint32_t o = (uint32_t)(h.lo >> (8 * jo)) & 0xff;  // (jo <= 6)
-    const uint32_t on = o >= 252 ? 1u << (o - 252 < 2 ? o - 252 : 2) : 0u;
-    return (int32_t)(jo + 1 + on);
-}
+// (jadv_fast, the speculative walks' step: ez_k2_parse.h)
 
 // ---- 0: chunks per stream
 __global__ __launch_bounds__(1024) void kj_init(DecompressArgs A, JWork W) {
     __shared__ uint32_t part[1024];
     const uint32_t t = threadIdx.x;
     uint32_t carry = 0;
+    // the real extents against the ones the workspace holds (every thread reads the same four offsets);
+    // past them, only head and cbase (sized by count) are written: every stream handed over, no chunks
+    const bool over = A.in_off[A.count] - A.in_off[0] > W.in_ext || A.out_off[A.count] - A.out_off[0] > W.out_ext;
+    if (over && t == 0) W.pass[kJPasses] = 1;
     for (uint32_t base = 0; base < (uint32_t)A.count; base += 1024) {
         const uint32_t s = base + t;
         uint32_t nch = 0;
-        if (s < A.count) {
+        if (s < A.count && over) {
+            JHead h{};
+            h.state = 1;
+            h.bsl = -1;
+            W.head[s] = h;
+        } else if (s < A.count) {
             const uint64_t nb = A.in_off[s + 1] - A.in_off[s];
             const uint64_t cap = A.out_off[s + 1] - A.out_off[s];
             nch = nb == 0 ? 1u : (uint32_t)((nb + W.jc - 1) / W.jc);
@@ -263,6 +258,7 @@ __global__ __launch_bounds__(1024) void kj_init(DecompressArgs A, JWork W) {
 __global__ __launch_bounds__(64) void kj_spec(DecompressArgs A, JWork W) {
     __shared__ uint32_t bm[64][kJW + 1];
     __shared__ __attribute__((aligned(16))) uint8_t stage[kJStage];
+    if (kj_guarded(W)) return;
     const uint32_t lane = threadIdx.x;
     const uint32_t total = W.cbase[A.count];
     const uint32_t c = blockIdx.x * 64 + lane;
@@ -307,6 +303,7 @@ __device__ __forceinline__ int32_t kj_walk_true(const JWork &W, uint32_t cg, con
 
 __global__ __launch_bounds__(64) void kj_verify(DecompressArgs A, JWork W) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[kJStage];
+    if (kj_guarded(W)) return;
     const uint32_t total = W.cbase[A.count];
     const uint32_t c = blockIdx.x * 64 + threadIdx.x;
     bool live = c < total;
@@ -342,6 +339,7 @@ __global__ __launch_bounds__(64) void kj_verify(DecompressArgs A, JWork W) {
 }
 
 __global__ __launch_bounds__(64) void kj_fix(DecompressArgs A, JWork W) {
+    if (kj_guarded(W)) return;
     const uint32_t s = blockIdx.x, lane = threadIdx.x;
     JHead &H = W.head[s];
     if (H.state) return;
@@ -405,6 +403,7 @@ __global__ __launch_bounds__(64) void kj_fix(DecompressArgs A, JWork W) {
 // stream's array once the chunks' positions are known), the longest distance, Break positions
 __global__ __launch_bounds__(64) void kj_tok(DecompressArgs A, JWork W) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[kJStage];
+    if (kj_guarded(W)) return;
     const uint32_t total = W.cbase[A.count];
     const uint32_t c = blockIdx.x * 64 + threadIdx.x;
     bool live = c < total;
@@ -461,6 +460,7 @@ __global__ __launch_bounds__(64) void kj_tok(DecompressArgs A, JWork W) {
 
 // ---- 2b: token and output positions of the chunks; the stream's checks (wave per stream)
 __global__ __launch_bounds__(64) void kj_scan(DecompressArgs A, JWork W, uint64_t *tok_alloc) {
+    if (kj_guarded(W)) return;
     const uint32_t s = blockIdx.x, lane = threadIdx.x;
     JHead &H = W.head[s];
     if (H.state) return;
@@ -526,6 +526,7 @@ __global__ __launch_bounds__(64) void kj_scan(DecompressArgs A, JWork W, uint64_
 
 // ---- 2c: the chunks' records into the stream's array, positions from the stream's start (block per chunk)
 __global__ __launch_bounds__(64) void kj_place(DecompressArgs A, JWork W) {
+    if (kj_guarded(W)) return;
     const uint32_t c = blockIdx.x;
     if (c >= W.cbase[A.count]) return;
     const uint32_t s = chunk_stream(W.cbase, (uint32_t)A.count, c);
@@ -599,6 +600,7 @@ __device__ __forceinline__ void kj_piece(const DecompressArgs &A, const JWork &W
 }
 
 __global__ __launch_bounds__(256) void kj_expand(DecompressArgs A, JWork W) {
+    if (kj_guarded(W)) return;
     const uint64_t ob = A.out_off[0], g0 = jg0(A), end = A.out_off[A.count];
     const uint64_t hst = A.c_on ? ob - A.c_hist : ob;  // (c_on) the history [hst, ob): final bytes, pointing at themselves
     for (uint64_t g = g0 + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; g < end; g += (uint64_t)gridDim.x * blockDim.x * 16) {
@@ -645,7 +647,7 @@ __global__ __launch_bounds__(256) void kj_expand(DecompressArgs A, JWork W) {
 
 // ---- 4: one pointer-jumping pass (returns at once when the pass before changed nothing)
 __global__ __launch_bounds__(256) void kj_jump(DecompressArgs A, JWork W, int pass) {
-    if (pass > 0 && W.pass[pass - 1] == 0) return;
+    if (kj_guarded(W) || (pass > 0 && W.pass[pass - 1] == 0)) return;
     const uint64_t end = A.out_off[A.count] - jg0(A);  // (ptr counts from g0)
     bool changed = false;
     for (uint64_t g = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; g < end; g += (uint64_t)gridDim.x * blockDim.x * 4) {
@@ -678,6 +680,7 @@ __global__ __launch_bounds__(256) void kj_jump(DecompressArgs A, JWork W, int pa
 
 // ---- 5a: every copied byte from its resolved source
 __global__ __launch_bounds__(256) void kj_gather(DecompressArgs A, JWork W) {
+    if (kj_guarded(W)) return;
     const uint64_t g0 = jg0(A), end = A.out_off[A.count] - g0;
     uint8_t *o = A.out + g0;
     for (uint64_t g = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; g < end; g += (uint64_t)gridDim.x * blockDim.x * 4) {
@@ -690,7 +693,8 @@ __global__ __launch_bounds__(256) void kj_gather(DecompressArgs A, JWork W) {
 }
 
 // ---- 5b: results, or the stream to the exact decoder; a one-stream batch's Break positions from
-// (chunk, local position) to the stream's output positions
+// (chunk, local position) to the stream's output positions.  Under the guard every head says handed
+// over (kj_init), so only head and the slow list, both sized by count, are touched
 __global__ __launch_bounds__(256) void kj_final(DecompressArgs A, JWork W) {
     if (A.breaks && A.count == 1 && blockIdx.x == 0 && !W.head[0].state) {
         const uint64_t nbrk = A.breaks[0] < A.breaks_cap ? A.breaks[0] : A.breaks_cap;
@@ -759,7 +763,9 @@ uint64_t jump_workspace_bytes(uint64_t count, uint64_t in_total, uint64_t out_to
 }
 
 hipError_t batch_extents(const DecompressArgs &a, hipStream_t st, uint64_t *in_bytes, uint64_t *out_bytes) {
-    if (a.in_bytes || a.out_bytes) {
+    // the caller's hints only as a pair: one alone says nothing about the other extent, so it counts as
+    // unknown (kj_init checks the pair against the real offsets: a wrong hint costs speed, not memory)
+    if (a.in_bytes && a.out_bytes) {
         *in_bytes = a.in_bytes;
         *out_bytes = a.out_bytes;
         return hipSuccess;
@@ -817,6 +823,8 @@ hipError_t launch_decompress_jump(const DecompressArgs &a, hipStream_t st) {
     W.ptr = (uint32_t *)(w + o_ptr);
     W.pass = (uint32_t *)(w + o_pass);
     W.jc = jchunk(in_total);
+    W.in_ext = in_total;
+    W.out_ext = out_bytes;
     uint64_t *tok_alloc = (uint64_t *)(W.pass + kJPasses + 2);
     if ((e = hipMemsetAsync(W.pass, 0, 8 * (kJPasses + 2), st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.ptr, 0xff, 4 * out_total + 16, st)) != hipSuccess) return e;

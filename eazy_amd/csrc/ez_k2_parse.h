@@ -134,6 +134,44 @@ __host__ __device__ __forceinline__ int32_t fast_tok(uint64_t lo, int32_t &L, in
     return (L - 1) | (122 - (L - 1)) | (cp ? 253 - (int32_t)o : 0);
 }
 
+// bytes 1..4 of the 8 bytes hi:lo (v_alignbyte_b32 on the device; the host check compiles the shift)
+__host__ __device__ __forceinline__ uint32_t k2_alignbyte1(uint32_t hi, uint32_t lo) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_alignbyte(hi, lo, 1);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> 8);
+#endif
+}
+
+// The input bytes the token (or padding run, or meta) at the 16 bytes h takes, for the speculative
+// walks (kj_spec, kj_verify, kj_fix): the same advance as k2_scan for every form it accepts, from 32-bit
+// arithmetic on the header's first 8 bytes and no checks (a form k2_scan hands over advances by some
+// amount >= 1 here; kj_tok's full parse of the true chain then hands the stream over)
+__host__ __device__ __forceinline__ int32_t jadv_fast(V16 h) {
+    const uint32_t w0 = (uint32_t)h.lo, w1 = (uint32_t)(h.lo >> 32);
+    const uint32_t t0 = w0 & 0xff, l7 = t0 & 0x7f;
+    if (t0 == 0) return h.lo ? (int32_t)(__builtin_ctzll(h.lo) >> 3) : (h.hi ? 8 + (int32_t)(__builtin_ctzll(h.hi) >> 3) : 16);
+    if (t0 == 0x80) {
+        const uint32_t ml = (w0 >> 8) & 7;
+        return 2 + (ml == 7 ? 0 : (1 << ml));
+    }
+    const uint32_t ln = l7 >= 124 ? 1u << (l7 - 124 < 2 ? l7 - 124 : 2) : 0u;  // extra length bytes
+    const uint32_t j = 1 + ln;
+    if (!(t0 & 0x80)) {  // literal: the tag, then L bytes
+        const uint32_t lx = k2_alignbyte1(w1, w0);  // bytes 1..4
+        const uint32_t lmask = ln == 4 ? 0x3fffffffu : (1u << (8 * ln)) - 1;
+        const uint32_t L = l7 >= 124 ? 124u + (l7 >= 125 ? 256u : 0u) + (l7 >= 126 ? 65536u : 0u) + (lx & lmask) : l7;
+        const uint32_t adv = j + L;
+        return adv > 0x7fffffffu ? 0x7fffffff : (int32_t)adv;
+    }
+    // copy: the tag, the long prefix (0xff) if any, the offset byte and its 1, 2 or 4 extra bytes
+    const uint32_t bj = (uint32_t)(h.lo >> (8 * j)) & 0xff;  // (j <= 5)
+    const uint32_t jo = j + (bj == 0xff ? 1u : 0u);
+    const uint32_t o = (uint32_t)(h.lo >> (8 * jo)) & 0xff;  // (jo <= 6)
+    const uint32_t on = o >= 252 ? 1u << (o - 252 < 2 ? o - 252 : 2) : 0u;
+    return (int32_t)(jo + 1 + on);
+}
+
 // the checks on the decoder's state: output position pos in a slot of cap bytes and
 // bsl = log2 of the window after MetaReset (-1: none yet; updated here)
 __host__ __device__ __forceinline__ int k2_check(int r, const K2Tok &t, int32_t pos, int32_t cap, int32_t &bsl) {

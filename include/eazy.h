@@ -185,7 +185,11 @@ typedef struct {
     uint64_t max_len;        /* host hint: max input length of a stream (decompress: max slot; 0 = unknown) */
     /* decompress, host hints (ABI 2): in_off[count] - in_off[0] and out_off[count] - out_off[0],
      * both 0 = unknown.  With them the decoder route and its workspace need no read-back of the
-     * offsets, so the call never waits for the stream; compress ignores them. */
+     * offsets, so the call never waits for the stream; compress ignores them.  The hints count only
+     * as a pair: one alone is taken as unknown (the offsets are read back).  A wrong hint costs
+     * speed, never memory safety: the decoder checks the pair against the offsets on the device
+     * before it indexes anything sized from them, and a batch larger than its hints is decoded by
+     * the exact decoder (same bytes, sizes and statuses); larger hints only enlarge the workspace. */
     uint64_t in_bytes;
     uint64_t out_bytes;
 } ez_batch;
