@@ -182,6 +182,17 @@ def decompress_kernel_last() -> str:
     return chr(v) if v else ""
 
 
+def compress_route_last() -> str:
+    """The route the last batch compress of this process took (ez_compress_route_last):
+    's:lean g16 fw40', 's:parse t32', 'l', 'l:k1c', 'x', 'w:pl', 'w:win', 'w:view' (+ '+gtab');
+    '' none yet.  Tests and measurement."""
+    L = _lib()
+    L.ez_compress_route_last.argtypes = [C.c_char_p, C.c_int]
+    buf = C.create_string_buffer(64)
+    L.ez_compress_route_last(buf, len(buf))
+    return buf.value.decode()
+
+
 def k1c_stats(enable: bool) -> dict:
     """K1c's verdict counts so far (streams proven; fallen back to K1L for a chunk error or
     re-visit, no common copy end, a changed judgement, the record slot; path segments), then
@@ -724,10 +735,13 @@ def decompress_batch_multi(comp, comp_off, out_off, block_size_limit: int = 0, d
 
 
 def compress_batch_writes(data, in_off, write_idx, write_end, block: int = MiB, htable: int = 1024,
-                          append_magic: bool = True, stream=None) -> CompressedBatch:
+                          append_magic: bool = True, stream=None, max_len: int | None = None,
+                          max_writes: int | None = None, out: CompressedBatch | None = None) -> CompressedBatch:
     """K1 for multi-Write streams: stream s receives the Writes k = write_idx[s]
     .. write_idx[s+1]-1, Write k ending at data[write_end[k]] (CUDA int64 tensors).
-    Its slot holds the bytes Go's sink receives over those Write calls."""
+    Its slot holds the bytes Go's sink receives over those Write calls.  max_len and
+    max_writes state the host hints (default: computed from the batch); out: the slots to
+    fill (default: allocated with the documented capacity)."""
     import torch
 
     _need_cuda(data, in_off, write_idx, write_end)
@@ -736,15 +750,18 @@ def compress_batch_writes(data, in_off, write_idx, write_end, block: int = MiB, 
     n = in_off[1:] - in_off[:-1]
     cap = (n + (n >> 2) + 32 + 5 * nw + 15) & ~15  # ez_compress_bound + a trailing literal tag per Write
     slot_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=data.device), torch.cumsum(cap, 0)])
-    total = int(slot_off[-1].item())
-    out = CompressedBatch(
-        torch.empty(total + 16, dtype=torch.uint8, device=data.device),
-        slot_off,
-        torch.empty(count, dtype=torch.int64, device=data.device),
-        torch.empty(count, dtype=torch.int32, device=data.device),
-    )
-    max_len = int((in_off[1:] - in_off[:-1]).max().item()) if count else 0
-    max_writes = int(nw.max().item()) if count else 1
+    if out is None:
+        total = int(slot_off[-1].item())
+        out = CompressedBatch(
+            torch.empty(total + 16, dtype=torch.uint8, device=data.device),
+            slot_off,
+            torch.empty(count, dtype=torch.int64, device=data.device),
+            torch.empty(count, dtype=torch.int32, device=data.device),
+        )
+    if max_len is None:
+        max_len = int((in_off[1:] - in_off[:-1]).max().item()) if count else 0
+    if max_writes is None:
+        max_writes = int(nw.max().item()) if count else 1
     b = _Batch(data.data_ptr(), in_off.data_ptr(), out.slots.data_ptr(), out.slot_off.data_ptr(),
                out.sizes.data_ptr(), out.status.data_ptr(), count, max_len)
     L = _lib()

@@ -1237,7 +1237,8 @@ static int compress_batch_impl(int64_t block, int64_t htable, int flags, const e
     // multi-Write streams: K1s when it takes them (fresh streams, 2 x stream <= block), else the
     // general kernel (one wave per stream, the history read from the stream's earlier Writes)
     if (write_idx && b->count == 0) return EZ_OK;
-    const bool split_mw = write_idx && ez::split_stride_words(a) != 0;
+    // (a forced 'w' keeps them off K1s, as it does single Writes)
+    const bool split_mw = write_idx && !ez::compress_forced_general() && ez::split_stride_words(a) != 0;
     auto words_of = [&](const ez::CompressArgs &x) { return split_mw ? ez::split_scratch_words(x) : ez::compress_scratch_words(x); };
     uint64_t words = words_of(a);
     // the scratch of this (device, stream) stays leased through the launches: another host thread
@@ -1308,6 +1309,17 @@ extern "C" int ez_select_decompress_kernel(int kind) {
 }
 
 extern "C" int ez_decompress_kernel_last(void) { return ez::last_decompress_variant(); }
+
+extern "C" int ez_compress_route_last(char *buf, int cap) {
+    const char *r = ez::last_compress_route();
+    const int n = (int)strlen(r);
+    if (buf && cap > 0) {
+        const int k = n < cap - 1 ? n : cap - 1;
+        memcpy(buf, r, (size_t)k);
+        buf[k] = 0;
+    }
+    return n;
+}
 
 extern "C" int ez_compress_k1c_stats(int enable, uint64_t *counts) {
     ez::k1c_stats(enable, counts);

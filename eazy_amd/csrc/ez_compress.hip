@@ -162,6 +162,17 @@ __device__ void compress_stream(const CompressArgs &A, uint64_t s, uint8_t *smem
     constexpr bool SMALL = !RING && !MWP;
     typedef typename std::conditional<SMALL, int32_t, int64_t>::type I;
     const int lane = lane_id();
+    // the launcher sized the LDS staging area (PL) and chose the 32-bit positions (SMALL) from max_len:
+    // a fresh stream longer than the hint (a multi-Write stream: its Writes together) is refused, as
+    // K1s and K1x refuse it -- nothing staged, parsed or written.  Writer handles set max_len themselves,
+    // and K1x's resume calls never get here with such a stream (spec[s].flags)
+    if (!RING && A.max_len != 0 && A.in_off[s + 1] - A.in_off[s] > A.max_len) {
+        if (lane == 0) {
+            A.out_size[s] = 0;
+            if (A.status) A.status[s] = EZ_EINVAL;
+        }
+        return;
+    }
     const uint64_t ib = A.in_off[s];
     // multi-Write streams (A.write_idx; fresh streams, or the handle's stream with RING): Writes k = write_idx[s] ..
     // write_idx[s+1]-1 of one Writer, Write k ending at in[write_end[k]]; each Write's loop runs to
@@ -171,6 +182,14 @@ __device__ void compress_stream(const CompressArgs &A, uint64_t s, uint8_t *smem
     if (mw) {
         wk = A.write_idx[s];
         wlast = A.write_idx[s + 1];
+        // more Writes than the caller's max_writes: refused with K1s's status (k1_parse)
+        if (!RING && wlast > wk && wlast - wk > A.max_writes) {
+            if (lane == 0) {
+                A.out_size[s] = 0;
+                if (A.status) A.status[s] = EZ_ESTUCK;
+            }
+            return;
+        }
     }
     uint64_t wbeg = ib;  // the current Write's first byte (index into A.in)
     I n = (I)((mw ? (wk < wlast ? A.write_end[wk] : ib) : A.in_off[s + 1]) - ib);
@@ -734,6 +753,10 @@ char compress_variant(const CompressArgs &a) {
 bool compress_forced_general() { return forced_variant() == 'w'; }
 bool compress_forced_long() { return forced_variant() == 'l'; }
 
+static std::atomic<const char *> g_last_route{""};  // a string literal of the launcher that stored it
+void set_compress_route(const char *route) { g_last_route = route; }
+const char *last_compress_route() { return g_last_route; }
+
 hipError_t launch_compress(const CompressArgs &a, hipStream_t st) {
     if (a.count == 0) return hipSuccess;
     const char v = compress_variant(a);
@@ -763,6 +786,11 @@ hipError_t launch_general(const CompressArgs &a, hipStream_t st) {
     if (!htl && !ring) grid = grid < 2048 ? grid : 2048;  // global scratch hash tables
     if (grid > (1u << 30)) grid = 1u << 30;
     const unsigned g = (unsigned)grid;
+    if (!ring) {  // (a fresh batch's route; the 64-bit multi-Write variant of launch_variant takes the global view)
+        const bool view = !pl && b.win_bytes == 0;
+        if (htl) set_compress_route(pl ? "w:pl" : (view ? "w:view" : "w:win"));
+        else set_compress_route(pl ? "w:pl+gtab" : (view ? "w:view+gtab" : "w:win+gtab"));
+    }
     if (pl) {
         if (htl) return ring ? launch_variant<true, true, true>(b, st, lds, g) : launch_variant<true, true, false>(b, st, lds, g);
         return ring ? launch_variant<true, false, true>(b, st, lds, g) : launch_variant<true, false, false>(b, st, lds, g);

@@ -602,6 +602,7 @@ hipError_t launch_compress_spec(const CompressArgs &a0, uint8_t *scratch, hipStr
         (void)hipMemcpy(nl, B.nact, 8, hipMemcpyDeviceToHost);
         fprintf(stderr, "K1x: %d rounds, %u literal records; active after the rounds: %u\n", rounds(), nl[1], nl[0]);
     }
+    set_compress_route("x");  // (after the general kernel's and K1L's launches above, which store theirs)
     return hipSuccess;
 }
 

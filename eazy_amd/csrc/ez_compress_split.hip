@@ -247,6 +247,9 @@ __global__ __launch_bounds__(64, 5) void k1_parse(CompressArgs A, uint32_t strid
         wk = A.write_idx[s];
         wlast = A.write_idx[s + 1] - 1;
         if (A.write_idx[s + 1] <= wk) err = EZ_EINVAL;
+        // more Writes than the caller's max_writes: their end markers have no record reserved (rec_cap);
+        // refused here with the status of the record guard below, whether or not the records would run out
+        else if (!err && A.write_idx[s + 1] - wk > A.max_writes) err = EZ_ESTUCK;
         else wend = (int32_t)(A.write_end[wk] - A.in_off[s]);
     }
     bool live = have && !err && (n >= 4 || wk < wlast);
@@ -2417,10 +2420,13 @@ __device__ __forceinline__ void emit_stream(const CompressArgs &A, const uint64_
 
     // header (writer.go:495-517): magic + reset, or reset alone
     const int32_t H = spec ? (int32_t)A.spec[s].op : (A.header ? (A.append_magic ? 9 : 3) : 0);
-    if (!spec && H > cap) {
+    // a stream the parse refused before its first record (longer than max_len, more Writes than
+    // max_writes) gets its status, size 0 and no byte in its slot, as K1x's refused streams
+    const bool refused = !spec && err != 0 && m == 0;
+    if (refused || (!spec && H > cap)) {
         if (lane == 0) {
             A.out_size[s] = 0;
-            if (A.status) A.status[s] = EZ_ENOSPC;
+            if (A.status) A.status[s] = refused ? err : EZ_ENOSPC;
         }
         return;
     }
@@ -2639,11 +2645,12 @@ __global__ __launch_bounds__(64) void ke_scan(CompressArgs A, const uint4 *recs,
     int err = (int)(pr >> 48);
     const bool spec = A.spec_mode != 0;
     uint64_t *inf = E.info + 4 * s;
-    if (!spec && H > cap) {  // not even the header
+    const bool refused = !spec && err != 0 && m == 0;  // by the parse, before its first record (emit_stream's rule)
+    if (refused || (!spec && H > cap)) {  // not even the header
         if (lane == 0) {
             inf[0] = 0, inf[3] = 1;
             A.out_size[s] = 0;
-            if (A.status) A.status[s] = EZ_ENOSPC;
+            if (A.status) A.status[s] = refused ? err : EZ_ENOSPC;
         }
         return;
     }
@@ -2834,6 +2841,7 @@ hipError_t launch_split_g(const CompressArgs &a, uint64_t *recs, hipStream_t st)
     // bit 1 around the next window's load; EZ_K1S_PRIO=0|1|2|3 (A/B, same box: 3.58 / 3.52 /
     // 3.58 / 3.53 ms at C1)
     static const int prio = knob("EZ_K1S_PRIO", 1);
+    set_compress_route(T16 ? (MW ? "s:parse t16 mw" : "s:parse t16") : (MW ? "s:parse t32 mw" : "s:parse t32"));
     hipLaunchKernelGGL((k1_parse<G, T16, MW>), dim3(grid), dim3(64), (size_t)stride * 4 * S + pad, st, a, stride, tw, recs, rcap,
                        prio);
     hipError_t e = hipGetLastError();
@@ -2928,20 +2936,22 @@ hipError_t launch_lean(const CompressArgs &a, uint64_t *recs, hipStream_t st) {
     static const bool persist = knob("EZ_K1S_PERSIST", 0) != 0;
     const size_t lds = (size_t)stride * 4 * S + (lw && msk ? (size_t)kWinLdsBytes * S : 0) + pad;
     hipError_t e;
+    const char *route;  // group width and forward cap; the A/B knobs' variants carry a third word
     if (g8) {
-        if (t12) e = launch_lean_v<12, true, 40, 8>(a, recs, stride, tw, lds, prio, edge, persist, st);
-        else if (w40) e = launch_lean_v<16, true, 40, 8>(a, recs, stride, tw, lds, prio, edge, persist, st);
-        else e = launch_lean_v<16, true, 24, 8>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        if (t12) route = "s:lean g8 fw40 t12", e = launch_lean_v<12, true, 40, 8>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        else if (w40) route = "s:lean g8 fw40", e = launch_lean_v<16, true, 40, 8>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        else route = "s:lean g8 fw24", e = launch_lean_v<16, true, 24, 8>(a, recs, stride, tw, lds, prio, edge, persist, st);
     } else if (lw && msk) {
-        if (t12) e = launch_lean_v<12, true, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
-        else if (w40) e = launch_lean_v<16, true, 40>(a, recs, stride, tw, lds, prio, edge, persist, st);
-        else e = launch_lean_v<16, true, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        if (t12) route = "s:lean g16 fw24 t12", e = launch_lean_v<12, true, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        else if (w40) route = "s:lean g16 fw40", e = launch_lean_v<16, true, 40>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        else route = "s:lean g16 fw24", e = launch_lean_v<16, true, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
     } else if (t12)
-        e = launch_lean_v<12, false, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        route = "s:lean g16 fw24 t12 roll", e = launch_lean_v<12, false, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
     else if (msk)
-        e = launch_lean_v<16, false, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        route = "s:lean g16 fw24 roll", e = launch_lean_v<16, false, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
     else
-        e = launch_lean_v<0, false, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
+        route = "s:lean g16 fw24 dpp", e = launch_lean_v<0, false, 24>(a, recs, stride, tw, lds, prio, edge, persist, st);
+    set_compress_route(route);
     if (e != hipSuccess) return e;
 #if (EZ_EXP & 2097152)
     {  // (timing builds) waves active over time, and when each XCC's last wave ends
@@ -3361,6 +3371,7 @@ static hipError_t launch_chunk(const CompressArgs &a, uint8_t *recs, hipStream_t
     if (lw) hipLaunchKernelGGL(k1_long<true>, dim3(lgrid), dim3(64), llds, st, a, (uint32_t)a.hs, (uint4 *)recs, rcap, S, B.sinfo + 1, kKcInfo);
     else hipLaunchKernelGGL(k1_long<false>, dim3(lgrid), dim3(64), llds, st, a, (uint32_t)a.hs, (uint4 *)recs, rcap, S, B.sinfo + 1, kKcInfo);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    set_compress_route("l:k1c");
     return launch_emit_wide(a, (const uint4 *)recs, rcap, ews, st);
 }
 
@@ -3392,6 +3403,7 @@ hipError_t launch_long(const CompressArgs &a, uint8_t *recs, hipStream_t st) {
     else hipLaunchKernelGGL(k1_long<false>, dim3(grid), dim3(64), lds, st, a, (uint32_t)a.hs, (uint4 *)recs, rcap, S, nullptr, 0u);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    set_compress_route("l");
     return launch_emit_wide(a, (const uint4 *)recs, rcap, recs + up256(a.count * rcap * sizeof(WideRec)), st);
 }
 

@@ -157,6 +157,10 @@ hipError_t launch_compress_split(const CompressArgs &a, uint32_t *scratch, hipSt
 // the K1 kernel a batch launch takes: 's' K1s (parse + token writer), 'w' general wave per stream
 char compress_variant(const CompressArgs &a);
 void select_compress_variant(int v);  // 0 = automatic, else a variant letter (tests, A/B)
+// the route of the last batch compress (ez_compress_route_last): every launcher stores the name of
+// what it launched, a string literal; a launcher that calls another one (K1x) stores its own last
+void set_compress_route(const char *route);
+const char *last_compress_route();
 // K1L: the lean parse for long fresh streams (ez_compress_split.hip); resumes K1x's streams (spec_mode 2)
 bool long_applies(const CompressArgs &a);
 uint64_t long_scratch_bytes(const CompressArgs &a);

@@ -182,7 +182,12 @@ typedef struct {
     uint64_t *out_size;      /* count: bytes written into each slot */
     int32_t *status;         /* count: EZ_* per stream (may be NULL) */
     uint64_t count;
-    uint64_t max_len;        /* host hint: max input length of a stream (decompress: max slot; 0 = unknown) */
+    /* host hint: max input length of a stream (decompress: max slot; 0 = unknown).  Compress: the hint
+     * sizes the route's scratch and picks the route, nothing else -- a larger hint gives the same
+     * bytes; a stream of exactly max_len bytes is accepted; a longer one (a multi-Write stream: its
+     * Writes together) gets status EZ_EINVAL and out_size 0, nothing is written into its slot and
+     * the other streams are untouched; 0 = unknown takes the general kernel. */
+    uint64_t max_len;
     /* decompress, host hints (ABI 2): in_off[count] - in_off[0] and out_off[count] - out_off[0],
      * both 0 = unknown.  With them the decoder route and its workspace need no read-back of the
      * offsets, so the call never waits for the stream; compress ignores them.  The hints count only
@@ -203,7 +208,9 @@ int ez_compress_batch(int64_t block, int64_t htable, int flags, const ez_batch *
  * sink receives over the k calls).  Stream s receives the Writes
  * k = write_idx[s] .. write_idx[s+1]-1 (device arrays, write_idx[count+1]);
  * Write k is in[prev .. write_end[k]) with prev = in_off[s] for the first.
- * max_writes: the most Writes of one stream (host hint).  Slots need
+ * max_writes: the most Writes of one stream (host hint; it reserves the records of the
+ * Writes' ends).  A stream with more Writes is refused: status EZ_ESTUCK, out_size 0,
+ * nothing written into its slot, the other streams untouched.  Slots need
  * ez_compress_bound(n) + 5 bytes per Write.  Streams of any length: K1s takes
  * batches with 2 x length <= block, the general kernel the others. */
 int ez_compress_batch_writes(int64_t block, int64_t htable, int flags, const ez_batch *b, const uint64_t *write_idx,
@@ -281,6 +288,13 @@ int ez_select_decompress_kernel(int kind);
 /* Introspection: the first K2 kernel the last ez_decompress_batch call of this process ran
  * ('r', 't', 'w'; 'e' the exact decoder alone; 0 none yet). */
 int ez_decompress_kernel_last(void);
+/* Introspection (tests, measurement): the route the last ez_compress_batch / _writes call of this
+ * process took, as a short NUL-terminated string; returns its length (0: none yet).  "s:lean g16 fw40"
+ * (k1_lean: lanes per stream, the judgement's forward bytes), "s:parse t32", "s:parse t16 mw"
+ * (k1_parse: table width, multi-Write), "l" (K1L), "l:k1c" (K1c, K1L behind it), "x" (K1x),
+ * "w:pl" / "w:win" / "w:view" (the general kernel: stream staged in LDS, 32 KiB LDS window, global
+ * view), "+gtab" appended when its hash tables are in global scratch. */
+int ez_compress_route_last(char *buf, int cap);
 /* Testing: K1c (the chunk-parallel parse of long fresh streams, which proves each stream's parse
  * is Go's or gives it to K1L) counts its verdicts while counting is on: counts (6 words, may be
  * NULL) gets {streams proven, chunk error or re-visit, no common copy end, a judgement changed,
