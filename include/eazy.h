@@ -216,7 +216,17 @@ int ez_compress_batch(int64_t block, int64_t htable, int flags, const ez_batch *
 int ez_compress_batch_writes(int64_t block, int64_t htable, int flags, const ez_batch *b, const uint64_t *write_idx,
                              const uint64_t *write_end, uint64_t max_writes, void *hip_stream);
 /* K3: exclusive scan of sizes -> packed_off[count+1], then gather the slots
- * densely into packed.  workspace >= ez_pack_workspace(count) device bytes. */
+ * densely into packed.  workspace >= ez_pack_workspace(count) device bytes.
+ * Stream s is slots[slot_off[s] .. slot_off[s] + sizes[s]); it lands at
+ * packed[packed_off[s] .. packed_off[s+1]).  slots, packed and every
+ * slot_off[s] may have any byte alignment (slot_off, sizes, packed_off and
+ * workspace are uint64 arrays, 8-aligned); sizes[s] may be 0; slots may lie in
+ * any order, with gaps, adjacent or overlapping (they are only read).
+ * packed_off[0] = 0 whatever slot_off[0] is, and only packed[0 .. packed_off[count])
+ * and packed_off[0 .. count] are written.  The source is read in whole aligned
+ * dwords that hold a byte of a stream, so up to 3 bytes either side of it (never
+ * outside a page the stream lies in; the bytes are read, not used).
+ * count == 0 writes packed_off[0] only.  Held by tests/test_gpu_k3_pack.py. */
 size_t ez_pack_workspace(uint64_t count);
 int ez_pack_batch(const uint8_t *slots, const uint64_t *slot_off, const uint64_t *sizes, uint64_t count,
                   uint8_t *packed, uint64_t *packed_off, void *workspace, void *hip_stream);
