@@ -236,7 +236,15 @@ int ez_pack_batch(const uint8_t *slots, const uint64_t *slot_off, const uint64_t
  * out_size[s] = bytes produced before it (out_size is required).
  * workspace >= ez_decompress_workspace(count) device bytes enables the
  * lane-per-stream fast decoder (streams it cannot take are handed to the
- * exact wave-per-stream decoder); NULL = exact decoder only. */
+ * exact wave-per-stream decoder); NULL = exact decoder only.
+ * Memory touched: in[0 .. in_off[count]) must be readable (the decoders' clamped loads may read
+ * any byte of it, bytes before in_off[0] included; none is read at or past in_off[count], and no
+ * result depends on a byte outside the streams), and in_off holds at least 16 bytes.  Nothing
+ * outside the slots is written.  A stream with status EZ_OK leaves its slot's bytes from
+ * out_size[s] on untouched; a stream with an error may leave part of its slot overwritten (a fast
+ * decoder's output before the hand-over), never a byte outside it.  A fast decoder takes only
+ * slots of at least 16 bytes and batches of at least 16 input bytes; the others go to the exact
+ * decoder.  Held by tests/test_gpu_k2r.py, test_gpu_k2t.py and test_gpu_k2j.py. */
 size_t ez_decompress_workspace(uint64_t count);
 int ez_decompress_batch(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
 

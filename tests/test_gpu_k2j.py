@@ -13,95 +13,23 @@ Every decode forces K2j, and checks, per stream: status, size and bytes equal th
 [out_off[s], out_off[s] + size) keeps its 0xA5 sentinel (slot slack and the bytes before out_off[0]
 included); and the streams K2j handed to the exact decoder (the workspace's first words: the count,
 then the stream indices) are exactly the ones expected -- none, for valid streams of the forms K2j
-takes.  All comparisons are exact equality."""
+takes.  All comparisons are exact equality.  The builders and the check (_run) live in
+tests/k2_streams.py, shared with the K2r and K2t suites."""
 
 import numpy as np
 import pytest
 
 import oracle as orc
+from k2_streams import HDR, META_RESET, SMALL_MAX, _forms, _need, _oracle, _run, cpy, lit, lit_to, meta, rb
 
 pytestmark = pytest.mark.gpu
 
-HDR = b"\x80\x02eazy\x80\x10\x14"  # magic, reset to a 1 MiB window
-LIT, CPY = 0x00, 0x80
-SMALL_MAX = 96 << 10  # jchunk: 256-byte chunks up to this much input in the batch, 1 KiB above
-META_MAGIC, META_VER, META_RESET, META_BREAK = 0 << 3, 1 << 3, 2 << 3, 3 << 3
 
-
-# ---------------------------------------------------------------- stream builders (host only)
-
-
-def _E():
-    import eazy_amd as ez
-
-    return ez.Encoder()
-
-
-def rb(rng, n):
-    return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
-
-
-def lit(body):
-    return _E().tag(b"", LIT, len(body)) + body
-
-
-def cpy(d, n):
-    """A copy of n bytes from d back, as Encoder.Offset writes it (d < n: the 0xff long prefix)."""
-    e = _E()
-    return e.offset(e.tag(b"", CPY, n), d, n)
-
-
-def cpy_long(d, n):
-    """The long prefix with a distance that does not need it (Decoder.Offset takes it all the same)."""
-    e = _E()
-    return e.tag(b"", CPY, n) + b"\xff" + e.offset(b"", d, 0)
-
-
-def meta(m, arg=b""):
-    return _E().meta(b"", m, len(arg)) + arg
-
-
-def lit_to(c, target, rng):
-    """c plus literals so that the stream is target bytes long."""
-    e = _E()
-    for extra in range(4):
-        c2 = c + lit(b"q") * extra
-        for tl in (1, 2, 3, 5):
-            n = target - len(c2) - tl
-            if n >= 1 and len(e.tag(b"", LIT, n)) == tl:
-                out = c2 + lit(rb(rng, n))
-                assert len(out) == target
-                return out
-    raise AssertionError((len(c), target))
+# ---------------------------------------------------------------- the streams (builders: k2_streams)
 
 
 def _trailer():
     return lit(b"tail") + cpy(3, 12)
-
-
-def _forms(rng):
-    """(name, bytes of the form, header length, whether it needs a 70,000-byte literal before it)"""
-    f = [
-        ("lit_len0", lit(rb(rng, 50)), 1, False),
-        ("lit_len1", lit(rb(rng, 200)), 2, False),
-        ("lit_len2", lit(rb(rng, 1000)), 3, False),
-        ("lit_len4", lit(rb(rng, 70000)), 5, False),
-        ("cpy_plain", cpy(30, 20), 2, False),
-        ("cpy_off1", cpy(320, 20), 3, False),
-        ("cpy_off2", cpy(720, 20), 4, False),
-        ("cpy_len1_off1", cpy(500, 200), 4, False),
-        ("cpy_len2", cpy(510, 500), 4, False),
-        ("cpy_off4", cpy(66044 + 20 + 100, 20), 6, True),
-        ("cpy_len4_run", cpy(1, 70000), 7, False),
-        ("cpy_long", cpy_long(40, 20), 3, False),
-        ("zero_region", cpy(0, 64), 3, False),
-        ("break", meta(META_BREAK), 2, False),
-        ("ver", meta(META_VER, b"\x00"), 3, False),
-        ("magic", meta(META_MAGIC, b"eazy"), 6, False),
-    ]
-    for n in (1, 15, 16, 17, 40):
-        f.append((f"pad{n}", bytes(n), n, False))
-    return f
 
 
 def seam_streams():
@@ -177,94 +105,7 @@ def filler():
     return _FILLER
 
 
-# ---------------------------------------------------------------- the check
-
-_ORC = {}
-
-
-def _oracle(b, cap):
-    key = (b, cap)
-    if key not in _ORC:
-        want, err, _ = orc.decompress(b, cap=cap)
-        _ORC[key] = (want, err)
-    return _ORC[key]
-
-
-def _need(b):
-    """The oracle's output length of a stream (its partial output, for a stream with an error)."""
-    return len(_oracle(b, max(1 << 20, 4 * len(b)))[0])
-
-
-def _slot(s, need):
-    n = need + 1 + s % 5
-    return n + 1 if n % 16 == 0 else n
-
-
-def _run(cuda, ins, jc, slots=None, handed="auto", hints=None, lead=5, kind="j"):
-    """Decode ins with K2j forced and check everything the module's docstring lists.
-    jc: the chunk size the batch must take (asserted from its input).  slots: {index: slot bytes}
-    overriding the default (the oracle's length plus 1..5 bytes, never a multiple of 16).
-    handed: the stream indices K2j must hand over ("auto": the ones the oracle gives an error or
-    that do not fit their slot; "all": every stream; None: not checked).  hints: f(in_bytes, out_bytes) -> kwargs."""
-    import torch
-
-    import eazy_amd as ez
-
-    count = len(ins)
-    total_in = sum(len(b) for b in ins)
-    assert (256 if total_in <= SMALL_MAX else 1024) == jc, (total_in, jc)
-    cap = [slots[s] if slots and s in slots else _slot(s, _need(b)) for s, b in enumerate(ins)]
-    coff = np.concatenate([[0], np.cumsum([len(b) for b in ins])]).astype(np.int64)
-    ooff = lead + np.concatenate([[0], np.cumsum(cap)]).astype(np.int64)
-    assert ooff[0] % 16 == 5
-    comp = torch.from_numpy(np.frombuffer(b"".join(ins) + bytes(64), np.uint8).copy()).to(cuda)
-    d_coff = torch.from_numpy(coff).to(cuda)
-    d_ooff = torch.from_numpy(ooff).to(cuda)
-    kw = hints(int(coff[-1] - coff[0]), int(ooff[-1] - ooff[0])) if hints else {}
-    res = []
-    for exact in (False, True):
-        out = torch.full((int(ooff[-1]) + 64,), 0xA5, dtype=torch.uint8, device=cuda)
-        sz = torch.full((count,), -7, dtype=torch.int64, device=cuda)
-        st = torch.full((count,), -7, dtype=torch.int32, device=cuda)
-        ws = torch.zeros(ez._lib().ez_decompress_workspace(count), dtype=torch.uint8, device=cuda)
-        ez.select_decompress_kernel("" if exact else "j")
-        try:
-            ez.decompress_batch(comp, d_coff, d_ooff, out=out, sizes=sz, status=st, workspace=ws, exact_only=exact, **kw)
-            torch.cuda.synchronize()
-            last = ez.decompress_kernel_last()
-        finally:
-            ez.select_decompress_kernel("")
-        if not exact:
-            assert last == kind, last
-        res.append((out.cpu().numpy(), sz.cpu().numpy(), st.cpu().numpy(), ws[: 4 * (count + 1)].cpu().numpy().view(np.uint32)))
-    (out, sz, st, w), (xout, xsz, xst, _) = res
-    bad = set()
-    inside = np.zeros(len(out), bool)
-    for s, b in enumerate(ins):
-        want, err = _oracle(b, cap[s])
-        o = int(ooff[s])
-        assert st[s] == xst[s] and sz[s] == xsz[s], (s, st[s], xst[s], sz[s], xsz[s])
-        assert 0 <= sz[s] <= cap[s], (s, sz[s])
-        n = int(sz[s])
-        inside[o : o + n] = True
-        assert out[o : o + n].tobytes() == xout[o : o + n].tobytes(), s
-        if err == 2:  # the oracle's output exceeded the slot
-            assert st[s] == ez.ENOSPC, (s, st[s])
-            bad.add(s)
-            continue
-        assert st[s] == err, (s, st[s], err)
-        assert n == len(want), (s, n, len(want))
-        assert out[o : o + n].tobytes() == want, s
-        if err != 0:
-            bad.add(s)
-    for name, a in (("K2j", out), ("exact", xout)):
-        stray = np.flatnonzero(~inside & (a != 0xA5))
-        assert stray.size == 0, (name, stray[:8], ooff[:4])
-    if kind == "j" and handed is not None:
-        got = set(int(x) for x in w[1 : 1 + int(w[0])])
-        assert int(w[0]) == len(got)
-        expect = bad if handed == "auto" else (set(range(count)) if handed == "all" else set(handed))
-        assert got == expect, (sorted(got), sorted(expect))
+# ---------------------------------------------------------------- the check (k2_streams._run)
 
 
 def _both(cuda, ins, handed="auto", slots=None, hints=None, filler_at=None):
@@ -380,7 +221,7 @@ def test_k2j_batch_counts(cuda, count):
 def test_k2j_takes_at_most_1024_streams(cuda):
     """A batch of 1,025 streams does not take K2j even when forced: K2t decodes it."""
     rng = np.random.default_rng(301)
-    _run(cuda, [_tiny(rng) for _ in range(1025)], 256, handed=None, kind="t")
+    _run(cuda, [_tiny(rng) for _ in range(1025)], 256, handed=None, last="t")
 
 
 def test_k2j_empty_streams_and_short_slot(cuda):

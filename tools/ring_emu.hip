@@ -1,6 +1,9 @@
 // Host emulation of the K2r decoder's per-lane code (ez_decompress_ring.hip):
 // the same source, compiled for the CPU, run stream by stream.
 //   ring_emu <in.bin> <offs.bin (u64 count+1)> <cap per stream> <out.bin> <sizes.bin (u64, ~0 = handed over)>
+//            [header window 1/0] [BlockSizeLimit] [caps.bin (u64 per stream, instead of the one cap)]
+// The output buffer starts as 0xA5 bytes: a read of a neighbour's slot or of bytes not yet written
+// does not pass for the zero history.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -27,8 +30,12 @@ int main(int argc, char **argv) {
     const uint64_t *offs = (const uint64_t *)ob.data();
     const uint64_t count = ob.size() / 8 - 1, cap = (uint64_t)atoll(argv[3]);
     std::vector<uint64_t> out_off(count + 1), size(count);
-    for (uint64_t s = 0; s <= count; s++) out_off[s] = s * cap;
-    std::vector<uint8_t> out(out_off[count] + 64);
+    std::vector<uint8_t> cb;
+    if (argc > 8) cb = slurp(argv[8]);
+    if (argc > 8 && cb.size() != 8 * count) return 2;
+    const uint64_t *caps = (const uint64_t *)cb.data();
+    for (uint64_t s = 0; s < count; s++) out_off[s + 1] = out_off[s] + (argc > 8 ? caps[s] : cap);
+    std::vector<uint8_t> out(out_off[count] + 64, 0xA5);
     std::vector<int32_t> st(count);
     ez::DecompressArgs a{};
     a.in = in.data();
@@ -38,6 +45,7 @@ int main(int argc, char **argv) {
     a.out_size = size.data();
     a.status = st.data();
     a.count = count;
+    a.block_size_limit = argc > 7 ? (int64_t)atoll(argv[7]) : 0;
     alignas(16) static uint8_t ring[1024];
     for (uint64_t s = 0; s < count; s++)
         if (!(hw ? ez::ring_one<true>(a, s, ring + 16) : ez::ring_one<false>(a, s, ring + 16))) size[s] = ~0ull;  // front guard
