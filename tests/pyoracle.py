@@ -209,6 +209,7 @@ class Writer:
         self._sink = bytearray()
         self.sink_writes = []
         self.fail_accept = None
+        self.trace = None  # a list: every accept and far skip of write() is appended (see _note)
         self.block = bytearray()
         self.ht = []
         self._init(block, htable)
@@ -251,6 +252,16 @@ class Writer:
             self.b += bytes([META, META_VER, self.ver & 0xFF])
         self.b += bytes([META, META_RESET, (self.bs & -self.bs).bit_length() - 1])
 
+    def _note(self, *ev) -> None:
+        """Optional record of the parse's decisions, positions relative to the Write's p:
+        (branch, i, candidate, ist, iend) per accepted copy, branch one of "window" (the
+        candidate lies in the block), "runlen" (in the pending literal), "zeros" (the zero
+        token) and "cut" (writeRunlen's
+        literal-only branch, ist = done); ("far", i) per candidate more than a block back;
+        ("short", i, candidate) per candidate in the block refused after the trims."""
+        if self.trace is not None:
+            self.trace.append(ev)
+
     def _literal(self, d: bytes, st: int, end: int) -> None:  # writer.go:519-522
         enc_tag(self.b, LITERAL, end - st)
         self.b += d[st:end]
@@ -264,7 +275,8 @@ class Writer:
             self.block[self.pos & self.mask] = d[k]
             self.pos += 1
 
-    def _write_zeros(self, p: bytes, done: int, i: int):  # writer.go:407-439
+    def _write_zeros(self, p: bytes, done: int, i: int, at: int = -1):  # writer.go:407-439 (at: the trace's acceptor)
+        cand = i
         iend = i
         while iend < len(p) and p[iend] == 0:
             iend += 1
@@ -275,6 +287,7 @@ class Writer:
         if done != i:
             self._literal(p, done, i)
             self._copy_data(p, done, i)
+        self._note("zeros", at, cand, i, iend)
         enc_tag(self.b, COPY, iend - i)
         self.b += bytes([OFF_LONG, 0])
         self._copy_data(p, i, iend)
@@ -282,7 +295,7 @@ class Writer:
 
     def _write_runlen(self, p: bytes, done: int, st: int, i: int):  # writer.go:441-489
         if st + 8 < len(p) and p[st : st + 8] == bytes(8):
-            return self._write_zeros(p, done, st)
+            return self._write_zeros(p, done, st, i)
         jf = 0
         while i + jf < len(p) and p[st + jf] == p[i + jf]:
             jf += 1
@@ -294,10 +307,12 @@ class Writer:
             return done, i + 1
         if i - st >= self.bs - 8:
             iend = done + i - st
+            self._note("cut", i, st, done, iend)
             self._literal(p, done, iend)
             self._copy_data(p, done, iend)
             return iend, iend
         ist, iend = i + jb, i + jf
+        self._note("runlen", i, st, ist, iend)
         self._literal(p, done, ist)
         self._copy_data(p, done, ist)
         enc_tag(self.b, COPY, iend - ist)
@@ -320,6 +335,7 @@ class Writer:
             self.ht[h] = (start + i) & 0xFFFFFFFF
             off = pos - self.pos
             if -off > self.bs:
+                self._note("far", i)
                 i += 1
                 continue
             if off >= 0 and i > done + off:
@@ -346,8 +362,10 @@ class Writer:
                 end -= diff
                 iend -= diff
             if end - st < MIN_COPY_CHUNK:
+                self._note("short", i, pos - start)
                 i += 1
                 continue
+            self._note("window", i, pos - start, ist, iend)
             if done < ist:
                 self._literal(p, done, ist)
                 self._copy_data(p, done, ist)
