@@ -1238,7 +1238,7 @@ static int compress_batch_impl(int64_t block, int64_t htable, int flags, const e
     // general kernel (one wave per stream, the history read from the stream's earlier Writes)
     if (write_idx && b->count == 0) return EZ_OK;
     // (a forced 'w' keeps them off K1s, as it does single Writes)
-    const bool split_mw = write_idx && !ez::compress_forced_general() && ez::split_stride_words(a) != 0;
+    const bool split_mw = write_idx && !ez::compress_forced_general() && ez::split_applies(a);
     auto words_of = [&](const ez::CompressArgs &x) { return split_mw ? ez::split_scratch_words(x) : ez::compress_scratch_words(x); };
     uint64_t words = words_of(a);
     // the scratch of this (device, stream) stays leased through the launches: another host thread

@@ -722,7 +722,7 @@ uint64_t compress_scratch_words(const CompressArgs &a) {
 }
 
 // K1 choice.  Fresh streams with 2n <= block and a table of at most 4096 entries take K1s
-// (ez_compress_split.hip: the parse kernel + the token writer); everything else -- writer handles
+// (ez_compress_split.hip routes it to a parse kernel + the token writer); everything else -- writer handles
 // (rings), Writes longer than half the window (C4), large tables -- takes the general
 // wave-per-stream kernel below, after K1x's rounds (ez_compress_spec.hip) for fresh single-Write
 // streams of 64 KiB and more.  EZ_K1=general or ez_select_compress_kernel('w') forces the general
@@ -746,7 +746,7 @@ char compress_variant(const CompressArgs &a) {
     const int forced = forced_variant();
     if (forced == 'w') return 'w';
     if (forced == 'l' && long_applies(a)) return 'l';  // K1L alone (tests, A/B)
-    if (split_stride_words(a) != 0 && forced != 'x') return 's';
+    if (split_applies(a) && forced != 'x') return 's';
     return spec_applies(a, forced == 'x') ? 'x' : 'w';
 }
 

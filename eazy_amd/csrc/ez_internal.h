@@ -148,9 +148,10 @@ struct DecompressArgs {
 uint64_t decompress_workspace_words(uint64_t count);
 
 hipError_t launch_compress(const CompressArgs &a, hipStream_t s);
-// K1s: fresh streams, parse kernel + token-writer kernel (ez_compress_split.hip);
-// scratch = 16-byte match records, split_scratch_words u32 words
-uint32_t split_stride_words(const CompressArgs &a);
+// K1s: fresh streams, parse kernel + token-writer kernel (routed by ez_compress_split.hip to the
+// families in ez_k1_*.hip); scratch = match records (+ the family's workspace), split_scratch_words
+// u32 words
+bool split_applies(const CompressArgs &a);  // K1s can take the batch
 uint64_t split_scratch_words(const CompressArgs &a);
 void select_split_table(bool t32);  // force the u32 exchange table (tests, A/B)
 hipError_t launch_compress_split(const CompressArgs &a, uint32_t *scratch, hipStream_t s);
@@ -161,7 +162,7 @@ void select_compress_variant(int v);  // 0 = automatic, else a variant letter (t
 // what it launched, a string literal; a launcher that calls another one (K1x) stores its own last
 void set_compress_route(const char *route);
 const char *last_compress_route();
-// K1L: the lean parse for long fresh streams (ez_compress_split.hip); resumes K1x's streams (spec_mode 2)
+// K1L: the lean parse for long fresh streams (ez_k1_long.hip); resumes K1x's streams (spec_mode 2)
 bool long_applies(const CompressArgs &a);
 uint64_t long_scratch_bytes(const CompressArgs &a);
 hipError_t launch_long(const CompressArgs &a, uint8_t *recs, hipStream_t s);
@@ -174,7 +175,7 @@ uint64_t long_ring_scratch_bytes(const CompressArgs &a);
 hipError_t launch_long_ring(const CompressArgs &a, uint8_t *recs, hipStream_t s);
 bool compress_forced_general();  // ez_select_compress_kernel('w') (tests, A/B)
 bool compress_forced_long();     // ez_select_compress_kernel('l'): K1L alone, without K1c (tests, A/B)
-// K1c (chunk-parallel K1L, ez_compress_split.hip): counting of its verdicts (ez_compress_k1c_stats)
+// K1c (chunk-parallel K1L, ez_k1_chunk.hip): counting of its verdicts (ez_compress_k1c_stats)
 bool chunk_applies(const CompressArgs &a);
 void k1c_stats(int enable, uint64_t *out);
 // K1x: the data-parallel first pass for long fresh single-Write streams (ez_compress_spec.hip)
@@ -203,9 +204,8 @@ DevCache &jump_cache();  // K2j's workspaces per (device, HIP stream)
 // in_off[count] - in_off[0], out_off[count] - out_off[0]: the caller's hints, else read back (waits)
 hipError_t batch_extents(const DecompressArgs &a, hipStream_t s, uint64_t *in_bytes, uint64_t *out_bytes);
 hipError_t launch_decompress_tok(const DecompressArgs &a, hipStream_t s);   // K2t, token-parallel wave per stream
-bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once)
+bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once, ez_k1_probe.hip)
 bool lds_mskor_in_lane_order();     // the LDS property k1_lean's one-atomic visit relies on (checked once)
-bool lds_mskor64_in_lane_order();   // the same on 12-bit fields of 64-bit words (k1_lean<12>)
 hipError_t launch_pack(const uint8_t *slots, const uint64_t *slot_off, const uint64_t *sizes, uint64_t count,
                        uint8_t *packed, uint64_t *packed_off, void *workspace, hipStream_t s);
 size_t pack_workspace(uint64_t count);

@@ -1,4 +1,4 @@
-// ez_k1_common.h — pieces of the group-per-stream K1 kernels (ez_compress_split.hip):
+// ez_k1_common.h — pieces of the group-per-stream K1 kernels (ez_k1_*.hip):
 // the byte view of a stream read through L1/L2, group
 // ballots/broadcasts, the branch-free Encoder.Tag / Encoder.Offset
 // (writer.go:537-597) and the cooperative exact match count.

@@ -322,8 +322,8 @@ def test_k1_edges_k1c_chunk_boundary(cuda):
     assert verdicts == {"I-" + k: v for k, v in K1C_VERDICTS.items()}, verdicts
 
 
-# Read from ez_compress_split.hip (kc_parse, long_loop's `keep`, kc_stitch_seq; the first pass's
-# guessed tables are off, so a chunk starts W before its start b with a zero table).  Chunk 0's
+# Read from ez_k1_chunk.hip and ez_k1_long.h (kc_parse, long_loop's `keep`, kc_stitch_seq; the first pass
+# starts from zero tables: a chunk starts W before its start b with a zero table).  Chunk 0's
 # parse is Go's and runs its windows while i < b1 + O (ev.stop), b1 = C; chunk 1 keeps the records
 # that end at or after b1; the stream is stitched at the first copy end >= b1 that both have, and
 # fails with "sync" when there is none.  Every later chunk start of these streams has a copy end

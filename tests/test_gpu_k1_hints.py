@@ -223,8 +223,8 @@ def assert_guards(cb, what):
 # ------------------------------------------------------------------ C1: a hint larger than the batch
 
 # (max_len, forced kind, htable, append_magic) -> route, block 1 MiB, 40 streams of <= 4096 bytes.
-# Read from ez_compress_split.hip launch_lean (8-lane groups: max_len > 4096; the 40-byte
-# judgement: max_len <= 16384 with 8-lane groups, else <= 8192), split_table / split_table_words
+# Read from ez_k1_lean.hip launch_lean (8-lane groups: max_len > 4096; the 40-byte
+# judgement: max_len <= 16384), split_table / split_table_words
 # (u16 table: max_len <= kMaxT16 = 65536; u32 table: <= kMaxT32 = 2^19 and 2 max_len <= block),
 # launch_compress_split (single Writes on the u32 table: launch_long), chunk_applies (K1c:
 # count <= 1024, max_len >= 2 C = 65536, not with 'l' forced); ez_compress_spec.hip spec_applies

@@ -1,4 +1,4 @@
-"""K1c (the chunk-parallel parse of long fresh streams, ez_compress_split.hip: kc_parse, kc_stitch,
+"""K1c (the chunk-parallel parse of long fresh streams, ez_k1_chunk.hip: kc_parse, kc_stitch,
 kc_gather, kc_v1, kc_v2, then K1L for the streams it cannot prove) against the oracle, through the
 C-ABI.  K1c takes the batches K1L would (single fresh Writes of 64 KiB and more, table <= 4096
 entries): C2's log streams directly, K1x's dense streams (longer than half the window) after its
