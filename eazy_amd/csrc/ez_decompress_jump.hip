@@ -37,7 +37,7 @@
 //  5. kj_gather writes every copied byte from its resolved source; kj_final reports each stream
 //     (out_size, status, Break positions, a Reader's end state) or hands it to the exact decoder.
 //
-// Continuation (DecompressArgs.c_on, a NewReader's read-ahead, ez_capi.hip stream_ahead): one stream
+// Continuation (DecompressArgs.c_on, a NewReader's read-ahead, ez_reader.hip stream_ahead): one stream
 // whose history (c_hist bytes) sits before out_off[0]; the chain stops before a token the input ends
 // inside of, a literal whose body runs past the input is output as far as it goes, and the end state
 // says where the input was left.

@@ -1,4 +1,4 @@
-// ez_internal.h — launch interface between the C-ABI (ez_capi.hip) and the
+// ez_internal.h — launch interface between the C-ABI (ez_capi.hip and its handle files) and the
 // gfx950 kernels (ez_compress.hip, ez_decompress.hip, ez_pack.hip).
 #pragma once
 
