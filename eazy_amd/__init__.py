@@ -132,6 +132,8 @@ def _lib():
     L.ez_decompress_workspace.restype = sz
     L.ez_decompress_workspace.argtypes = [C.c_uint64]
     L.ez_decompress_batch.argtypes = [i64, vp, vp, vp]
+    L.ez_decompressed_size_batch.argtypes = [i64, vp, vp, vp]
+    L.ez_decompressed_size_chunk.argtypes = [C.c_uint64]
     _L = L
     return L
 
@@ -819,6 +821,72 @@ def decompress_batch(comp, comp_off, out_off, block_size_limit: int = 0, out=Non
     ws = None if exact_only else workspace.data_ptr()
     _check(_lib().ez_decompress_batch(block_size_limit, C.byref(b), ws, _stream_ptr(stream)))
     return out, sizes, status
+
+
+def decompressed_size_chunk(max_len: int = 0) -> int:
+    """The chunk bytes K2z's fast kernel takes for a max_len hint (ez_decompressed_size_chunk)."""
+    return _lib().ez_decompressed_size_chunk(max_len)
+
+
+def decompressed_size_chunk_last() -> int:
+    """The chunk bytes the last decompressed_sizes call of this process ran with (0: the exact
+    decoder alone; -1: none yet)."""
+    return _lib().ez_decompressed_size_chunk_last()
+
+
+def decompressed_sizes(comp, comp_off, block_size_limit: int = 0, sizes=None, status=None, workspace=None,
+                       exact_only: bool = False, stream=None, max_len: int = 0):
+    """K2z: what decompress_batch would report for every stream comp[comp_off[s]:comp_off[s+1]]
+    given a slot that is large enough, without decoding -> (sizes, status): the decoded length
+    (for a stream that ends in an error, the bytes produced before it) and EZ_OK or that first
+    error.  No output buffer is needed or touched; sizes are 64-bit (an output over 4 GiB is
+    reported, not clamped).  max_len is an optional host hint, the longest INPUT stream in bytes:
+    it picks the fast kernel's chunk size and nothing else.  exact_only runs the exact decoder
+    alone.  Asynchronous on the stream."""
+    import torch
+
+    _need_cuda(comp, comp_off)
+    count = comp_off.numel() - 1
+    dev = comp.device
+    if sizes is None:
+        sizes = torch.empty(count, dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(count, dtype=torch.int32, device=dev)
+    if workspace is None and not exact_only:
+        workspace = torch.empty(_lib().ez_decompress_workspace(count), dtype=torch.uint8, device=dev)
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, None, sizes.data_ptr(), status.data_ptr(), count, max_len)
+    ws = None if exact_only else workspace.data_ptr()
+    _check(_lib().ez_decompressed_size_batch(block_size_limit, C.byref(b), ws, _stream_ptr(stream)))
+    return sizes, status
+
+
+def decompress_batch_sized(comp, comp_off, block_size_limit: int = 0, stream=None):
+    """Decode a batch whose decoded lengths the caller does not know -> (out, out_off, sizes,
+    status).  The sizes come from decompressed_sizes; the slots are laid out on the device (each
+    size rounded up to 16 bytes), the total and the largest slot are read back in one transfer
+    (which waits for the stream), and decompress_batch decodes with those as its hints.  sizes
+    and status are the decode's."""
+    import torch
+
+    _need_cuda(comp, comp_off)
+    count = comp_off.numel() - 1
+    dev = comp.device
+    import contextlib
+
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()  # (the torch steps on it too)
+    with ctx:
+        need, _ = decompressed_sizes(comp, comp_off, block_size_limit, stream=stream)
+        slot = (need + 15) & ~15
+        out_off = torch.zeros(count + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(slot, 0, out=out_off[1:])
+        total = largest = in_bytes = 0
+        if count:
+            back = torch.stack([out_off[-1], slot.max(), comp_off[-1] - comp_off[0]]).cpu()
+            total, largest, in_bytes = (int(v) for v in back)
+        out = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        _, sizes, status = decompress_batch(comp, comp_off, out_off, block_size_limit, out=out, stream=stream, max_len=largest,
+                                            in_bytes=in_bytes, out_bytes=total)
+    return out, out_off, sizes, status
 
 
 # ---------------------------------------------------------------- Dumper (reader.go:43-54, 545-768)

@@ -698,6 +698,14 @@ inline Err ReleaseCached(int device = -1) { return (Err)ez_release_cached(device
 inline Err DecompressBatch(int64_t block_size_limit, const ez_batch &b, void *workspace, void *hip_stream) {
     return (Err)ez_decompress_batch(block_size_limit, &b, workspace, hip_stream);
 }
+// ez_decompressed_size_batch (K2z): every stream's decoded length and status without decoding, into
+// b.out_size / b.status; b.out and b.out_off are not used (may be null), b.max_len is the longest
+// INPUT stream (0: unknown).  A caller sizes its slots from it and then calls DecompressBatch.
+inline Err DecompressedSizeBatch(int64_t block_size_limit, const ez_batch &b, void *workspace, void *hip_stream) {
+    const int st = ez_decompressed_size_batch(block_size_limit, &b, workspace, hip_stream);
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: DecompressedSizeBatch: out_size is required");
+    return (Err)st;
+}
 
 // Host-memory batches over several devices (ez_compress_batch_multi / ez_decompress_batch_multi):
 // bufs[k] is one Write to a fresh NewWriter(block, htable); out[k] gets its compressed bytes,

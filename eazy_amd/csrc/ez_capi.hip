@@ -286,6 +286,25 @@ extern "C" int ez_decompress_batch(int64_t block_size_limit, const ez_batch *b, 
     return EZ_OK;
 }
 
+extern "C" int ez_decompressed_size_batch(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream) {
+    if (device_count() <= 0) return EZ_EDEVICE;
+    if (!b->out_size) return EZ_EINVAL;
+    ez::DecompressArgs a{};
+    a.in = b->in;
+    a.in_off = b->in_off;
+    a.out_size = b->out_size;
+    a.status = b->status;
+    a.count = b->count;
+    a.block_size_limit = block_size_limit;
+    a.slow = (uint32_t *)workspace;
+    EZ_HIP(ez::launch_decompress_size(a, b->max_len, (hipStream_t)hip_stream));
+    return EZ_OK;
+}
+
+extern "C" int ez_decompressed_size_chunk(uint64_t max_len) { return ez::size_chunk(max_len); }
+
+extern "C" int ez_decompressed_size_chunk_last(void) { return ez::last_size_chunk(); }
+
 // Frees the device scratch the batch calls keep between calls (no reference counterpart; like a
 // caching allocator's empty_cache): the K1 / K1c scratch and K2j workspaces per (device, HIP stream),
 // the multi-device calls' pooled shard buffers and the Reader handles' shared K2j workspace, on

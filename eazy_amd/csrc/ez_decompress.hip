@@ -192,8 +192,9 @@ __global__ __launch_bounds__(64) void k2_decompress(DecompressArgs A) {
         d.limit = A.block_size_limit;
         d.req_magic = A.require_magic != 0;
         d.skip_meta = A.skip_unsupported_meta != 0;
-        uint8_t *out = A.out + A.out_off[s];
-        const int64_t cap = (int64_t)(A.out_off[s + 1] - A.out_off[s]);
+        // (the size query, A.dry: no slot -- nothing is stored, and no capacity ends the read)
+        uint8_t *out = A.dry ? nullptr : A.out + A.out_off[s];
+        const int64_t cap = A.dry ? (int64_t)1 << 62 : (int64_t)(A.out_off[s + 1] - A.out_off[s]);
         if (A.handle) {
             DecodeState &S = *A.st;
             d.bs = S.bs; d.mask = S.bs ? S.bs - 1 : 0; d.pos = S.pos; d.off = S.off; d.len = S.len;
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(64) void k2_decompress(DecompressArgs A) {
             const int64_t left = cap - total;
             int64_t m;
             if (left > 0) {
-                err = d_read_loop(d, left, &i, &m, false, lane);
+                err = d_read_loop(d, left, &i, &m, A.dry != 0, lane);
             } else {
                 err = d_read_loop(d, 1, &i, &m, true, lane);
                 if (m > 0) { err = EZ_ENOSPC; break; }
@@ -301,6 +302,33 @@ static hipError_t largest_slot(const DecompressArgs &a, hipStream_t st, uint64_t
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
     *mo = h;
     return hipSuccess;
+}
+
+// K2z: the decoded sizes.  With a workspace the fast kernel first, its hand-overs to the exact decoder
+// through the slow list as for the other decoders; without one the exact decoder alone.  Dry, both
+// ways: it reads every stream to EOF and stores nothing.
+static std::atomic<int> g_last_size_chunk{-1};
+int last_size_chunk() { return g_last_size_chunk; }
+
+hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hipStream_t st) {
+    DecompressArgs a = a0;
+    a.dry = 1;
+    a.out = nullptr;
+    a.out_off = nullptr;
+    const int chunk = a.slow ? size_route(max_len, a.count) : 0;
+    g_last_size_chunk = chunk;
+    if (a.count == 0) return hipSuccess;
+    if (!a.slow) {
+        const uint64_t grid = a.count < (1u << 30) ? a.count : (1u << 30);
+        hipLaunchKernelGGL(k2_decompress, dim3((unsigned)grid), dim3(64), 0, st, a);
+        return hipGetLastError();
+    }
+    hipError_t e = hipMemsetAsync(a.slow, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    if ((e = launch_size_fast(a, chunk, st)) != hipSuccess) return e;
+    const uint64_t exact_grid = a.count < 4096 ? a.count : 4096;
+    hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {

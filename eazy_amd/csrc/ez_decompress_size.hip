@@ -1,0 +1,169 @@
+// ez_decompress_size.hip — K2z: each stream's decoded length without decoding (ez_decompressed_size_batch).
+//
+// A decoded length depends on the tokens alone (Reader.read reader.go:143-216 adds every token's
+// length, whatever its bytes are), so the query reads token headers, skips every literal's body and
+// writes one u64 per stream.  One wave per stream, grid-stride over the streams.  The token chain is
+// cut inside the wave by speculation (the steps: ez_k2_size.h): the stream is taken in super-blocks
+// of 64 chunks of C input bytes, a chunk per lane.  Per super-block, which starts at the true chain's
+// position sb:
+//   stage    the super-block's 64 x C bytes and the 16 a header at its end reads go to LDS with
+//            16-byte loads, clamped to the stream (zeros past its end); every later step reads LDS;
+//   spec     kz_spec, a lane per chunk;
+//   verify   kz_verify from the predecessor's speculative exit; then, while a lane's assumed entry
+//            differs from its predecessor's verified exit, the lowest such lane re-walks (kz_fix; the
+//            lanes a spanning token covers take its end in the same round; at most 63 rounds,
+//            bounded by a counter that hands the stream over);
+//   sum      kz_sum over each lane's true chain;
+//   reduce   an in-order prefix over the lanes for the output bytes and the reset-before-any-output
+//            rule; the totals, the window and the flags are carried.
+// The next super-block starts at lane 63's true exit: a literal's body is never staged or read, however
+// long it is.  At the stream's end kz_end_ok decides: the wave writes out_size[s] and EZ_OK, or appends
+// the stream to the slow list, for the exact decoder run dry (ez_decompress.hip) -- every error, every
+// form k2_scan hands over, a MetaReset after output, a stream of 2 GiB or more.  Nothing else is written.
+#include <hip/hip_runtime.h>
+
+#include "ez_bytes.h"
+#include "ez_internal.h"
+#include "ez_k2_size.h"
+#include "ez_wave.h"
+
+namespace ez {
+namespace {
+
+template <int C>
+__global__ __launch_bounds__(64) void k2z_size(DecompressArgs A) {
+    constexpr int W = C / 32;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kz_stage_bytes(C)];
+    __shared__ uint32_t bm[kZLanes][W + 1];  // (+1: the lanes' rows on distinct banks)
+    const int lane = lane_id();
+    const int64_t limit = A.block_size_limit;
+    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
+        const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
+        const uint8_t *b = A.in + A.in_off[s];
+        bool bad = nb64 >= (1ull << 31);
+        const uint32_t nb = bad ? 0u : (uint32_t)nb64;
+        uint32_t sb = 0, maxd = 0;
+        uint64_t total = 0;
+        int32_t bsl = -1;
+        while (!bad && sb < nb) {
+            __syncthreads();  // (the previous super-block's reads are done)
+            const uint32_t need = nb - sb + 16 < kz_stage_bytes(C) ? nb - sb + 16 : kz_stage_bytes(C);
+            for (uint32_t o = (uint32_t)lane * 16; o < need; o += kWave * 16) {
+                const uint32_t y = sb + o;
+                V16 v{0, 0};
+                if (y + 16 <= nb) v = ld16v(b + y);
+                else if (y < nb) v = ld_clamped(b + y, b, b + nb);
+                typedef uint64_t __attribute__((aligned(8))) u64a;
+                *(u64a *)(stage + o) = v.lo;
+                *(u64a *)(stage + o + 8) = v.hi;
+            }
+            __syncthreads();
+            const KzWin w{stage, sb};
+            const uint32_t sexit = kz_spec<C>(w, sb, lane, nb, bm[lane]);
+            // lane k's entry is lane k-1's exit; lane 0 walked the true chain from sb
+            uint32_t a = __shfl_up(sexit, 1, kWave);
+            if (lane == 0) a = sb;
+            uint32_t x = lane == 0 ? sexit : kz_verify<C>(w, sb, lane, nb, bm[lane], sexit, a);
+            for (int round = 0;; round++) {
+                const uint32_t px = __shfl_up(x, 1, kWave);
+                const uint64_t wrong = wballot(lane > 0 && a != px);
+                if (wrong == 0) break;
+                if (round >= kZFixRounds) {
+                    bad = true;
+                    break;
+                }
+                const int jf = ffs64(wrong);
+                kz_fix<C>(w, sb, lane, nb, bm[lane], sexit, jf, (uint32_t)__shfl((int)x, jf - 1, kWave), a, x);
+            }
+            if (bad) break;
+            const KzSum r = kz_sum<C>(w, sb, lane, nb, a, x, lim32, limit);
+            uint64_t io = r.out;
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) {
+                const uint64_t v = __shfl_up(io, d, kWave);
+                if (lane >= d) io += v;
+            }
+            uint32_t md = r.maxd;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) md = max(md, (uint32_t)__shfl_xor((int)md, d, kWave));
+            maxd = max(maxd, md);
+            if (wballot((r.fl & kZBad) || kz_reset_bad(r.fl, total + io - r.out))) bad = true;
+            const uint64_t rm = wballot((r.fl & kZReset) != 0);
+            if (rm) bsl = (int32_t)((__shfl((int)r.fl, 63 - __builtin_clzll(rm), kWave) >> 8) & 0xff);
+            total += __shfl(io, kWave - 1, kWave);
+            sb = __shfl(x, kWave - 1, kWave);
+        }
+        if (!bad) bad = !kz_end_ok(sb, nb, total, bsl, maxd);
+        if (lane == 0) {
+            if (bad) {
+                const uint32_t at = atomicAdd(&A.slow[0], 1u);
+                A.slow[1 + at] = (uint32_t)s;
+            } else {
+                A.out_size[s] = total;
+                if (A.status) A.status[s] = EZ_OK;
+            }
+        }
+    }
+}
+
+// A lane per stream, for large batches of short streams: each lane walks its stream's whole chain in
+// order (kz_serial), reading 16 bytes per token through the caches.  No speculation, so nothing is
+// walked twice, and 64 streams share a wave's instructions: with enough short streams to fill the
+// chip's lanes that beats a wave per stream, whose lanes mostly repeat each other's walks on a stream
+// of a few dozen chunks (C1: DESIGN §4 K2z).
+__global__ __launch_bounds__(64) void k2z_lane(DecompressArgs A) {
+    const int64_t limit = A.block_size_limit;
+    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    for (uint64_t s = (uint64_t)blockIdx.x * kWave + threadIdx.x; s < A.count; s += (uint64_t)gridDim.x * kWave) {
+        const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
+        const uint8_t *b = A.in + A.in_off[s];
+        uint64_t total = 0;
+        bool ok = nb64 < (1ull << 31);
+        if (ok) {
+            const uint32_t nb = (uint32_t)nb64;
+            ok = kz_serial([=](uint32_t p) { return p + 16 <= nb ? ld16v(b + p) : ld_clamped(b + p, b, b + nb); }, nb, lim32, limit, total);
+        }
+        if (ok) {
+            A.out_size[s] = total;
+            if (A.status) A.status[s] = EZ_OK;
+        } else {
+            const uint32_t at = atomicAdd(&A.slow[0], 1u);
+            A.slow[1 + at] = (uint32_t)s;
+        }
+    }
+}
+
+}  // namespace
+
+// The chunk size for the caller's hint (the longest input stream, 0 = unknown): 64 bytes up to 4 KiB,
+// so that a C1-sized stream's ~2 KiB of input spans half a wave; 256 bytes up to 512 KiB; 1 KiB
+// above, for the few long streams of a bucket batch (fewer super-blocks, and a warm-up long enough
+// that almost every lane's speculation has met the true chain).  (Measured: DESIGN §4 K2z.)
+int size_chunk(uint64_t max_len) { return max_len == 0 ? 256 : (max_len <= 4096 ? 64 : (max_len <= (512u << 10) ? 256 : 1024)); }
+
+// Batches of at least this many streams whose hint says they are short take the lane-per-stream
+// kernel: from here on its one walk per stream, 64 streams to a wave, costs less than the wave
+// kernel's several walks per stream (an estimate from the wave kernel's C1 time per stream and the
+// length of one serial walk, not a measured crossover; below it the wave kernel's parallelism inside
+// a stream is what a few streams need).  Reported as chunk 1.
+constexpr uint64_t kZLaneStreams = 4096;
+int size_route(uint64_t max_len, uint64_t count) {
+    return max_len != 0 && max_len <= 4096 && count >= kZLaneStreams ? 1 : size_chunk(max_len);
+}
+
+hipError_t launch_size_fast(const DecompressArgs &a, int chunk, hipStream_t st) {
+    if (chunk == 1) {
+        const uint64_t blocks = (a.count + kWave - 1) / kWave;
+        hipLaunchKernelGGL(k2z_lane, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(64), 0, st, a);
+        return hipGetLastError();
+    }
+    // every wave of the chip busy at most (32 per CU); the streams beyond go round the grid
+    const unsigned grid = (unsigned)(a.count < 8192 ? a.count : 8192);
+    if (chunk == 64) hipLaunchKernelGGL(k2z_size<64>, dim3(grid), dim3(64), 0, st, a);
+    else if (chunk == 1024) hipLaunchKernelGGL(k2z_size<1024>, dim3(grid), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k2z_size<256>, dim3(grid), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace ez

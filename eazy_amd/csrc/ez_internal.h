@@ -142,6 +142,9 @@ struct DecompressArgs {
     int32_t c_bsl;
     uint64_t c_hist;
     int64_t c_pos0;
+    // batch, the size query (K2z, ez_decompressed_size_batch): the exact decoder reads every stream to
+    // EOF with an unbounded capacity and stores nothing; out and out_off are not touched (may be null)
+    int dry;
 };
 
 // words of workspace the two-level batch decoder needs
@@ -204,6 +207,14 @@ DevCache &jump_cache();  // K2j's workspaces per (device, HIP stream)
 // in_off[count] - in_off[0], out_off[count] - out_off[0]: the caller's hints, else read back (waits)
 hipError_t batch_extents(const DecompressArgs &a, hipStream_t s, uint64_t *in_bytes, uint64_t *out_bytes);
 hipError_t launch_decompress_tok(const DecompressArgs &a, hipStream_t s);   // K2t, token-parallel wave per stream
+// K2z, the decoded-size query: the fast kernel (ez_decompress_size.hip; a.slow set, streams it cannot
+// take go there) and then the exact decoder run dry, or that one alone (a.slow == nullptr); max_len:
+// the caller's hint, the longest input stream (0 = unknown), which picks the fast kernel's chunk
+hipError_t launch_decompress_size(const DecompressArgs &a, uint64_t max_len, hipStream_t s);
+int size_chunk(uint64_t max_len);  // the wave kernel's chunk bytes for a hint
+int size_route(uint64_t max_len, uint64_t count);  // 1: the lane-per-stream kernel; else the wave kernel's chunk
+int last_size_chunk();             // the route of the last query (0: the exact decoder alone; -1: none yet)
+hipError_t launch_size_fast(const DecompressArgs &a, int route, hipStream_t s);
 bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once, ez_k1_probe.hip)
 bool lds_mskor_in_lane_order();     // the LDS property k1_lean's one-atomic visit relies on (checked once)
 hipError_t launch_pack(const uint8_t *slots, const uint64_t *slot_off, const uint64_t *sizes, uint64_t count,

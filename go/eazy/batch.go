@@ -188,3 +188,81 @@ func compressStreams(streams [][][]byte, block, htable int) ([][]byte, error) {
 	}
 	return res, nil
 }
+
+// decompressedSizes: every stream's decoded length without decoding (ez_decompressed_size_batch).
+// The streams are staged into device memory, the query runs on the null stream with the fast kernel's
+// workspace, and the lengths and statuses come back; a stream's own error is returned as the
+// reference's Reader would report it, with the bytes it produced before it in sizes[k].
+func decompressedSizes(streams [][]byte, blockSizeLimit int) ([]uint64, []error, error) {
+	count := len(streams)
+	if count == 0 {
+		return nil, nil, nil
+	}
+	inOff := make([]uint64, count+1)
+	maxLen := 0
+	for k, s := range streams {
+		inOff[k+1] = inOff[k] + uint64(len(s))
+		if len(s) > maxLen {
+			maxLen = len(s)
+		}
+	}
+	host := make([]byte, 0, inOff[count])
+	for _, s := range streams {
+		host = append(host, s...)
+	}
+	var dIn, dInOff, dSize, dStatus, dWork unsafe.Pointer
+	defer func() {
+		for _, p := range []unsafe.Pointer{dIn, dInOff, dSize, dStatus, dWork} {
+			if p != nil {
+				C.hipFree(p)
+			}
+		}
+	}()
+	// every HIP call's result is checked: a failed copy must never hand back stale sizes as success
+	hip := func(r C.hipError_t) error {
+		if r != C.hipSuccess {
+			return ErrDevice
+		}
+		return nil
+	}
+	for _, a := range []struct {
+		p *unsafe.Pointer
+		n uint64
+	}{{&dIn, inOff[count]}, {&dInOff, 8 * uint64(count+1)}, {&dSize, 8 * uint64(count)}, {&dStatus, 4 * uint64(count)},
+		{&dWork, uint64(C.ez_decompress_workspace(C.uint64_t(count)))}} {
+		if err := hip(C.hipMalloc(a.p, C.size_t(a.n+16))); err != nil {
+			return nil, nil, err
+		}
+	}
+	if len(host) > 0 {
+		if err := hip(C.hipMemcpy(dIn, unsafe.Pointer(&host[0]), C.size_t(len(host)), C.hipMemcpyHostToDevice)); err != nil {
+			return nil, nil, err
+		}
+	}
+	if err := hip(C.hipMemcpy(dInOff, unsafe.Pointer(&inOff[0]), C.size_t(8*(count+1)), C.hipMemcpyHostToDevice)); err != nil {
+		return nil, nil, err
+	}
+	b := C.ez_batch{
+		in: (*C.uint8_t)(dIn), in_off: (*C.uint64_t)(dInOff), out_size: (*C.uint64_t)(dSize), status: (*C.int32_t)(dStatus),
+		count: C.uint64_t(count), max_len: C.uint64_t(maxLen),
+	}
+	if st := C.ez_decompressed_size_batch(C.int64_t(blockSizeLimit), &b, dWork, nil); st != C.EZ_OK {
+		return nil, nil, toErr(st, 0)
+	}
+	sizes := make([]uint64, count)
+	status := make([]int32, count)
+	// (hipMemcpy to host waits for the query's kernels on the null stream, and reports their faults)
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&sizes[0]), dSize, C.size_t(8*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, err
+	}
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&status[0]), dStatus, C.size_t(4*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, err
+	}
+	errs := make([]error, count)
+	for k := range streams {
+		if status[k] != 0 {
+			errs[k] = toErr(C.int(status[k]), 0)
+		}
+	}
+	return sizes, errs, nil
+}

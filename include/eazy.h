@@ -247,6 +247,26 @@ int ez_pack_batch(const uint8_t *slots, const uint64_t *slot_off, const uint64_t
  * decoder.  Held by tests/test_gpu_k2r.py, test_gpu_k2t.py and test_gpu_k2j.py. */
 size_t ez_decompress_workspace(uint64_t count);
 int ez_decompress_batch(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
+/* K2z: what ez_decompress_batch would report for every stream given a slot that is large enough,
+ * without decoding: out_size[s] = the bytes NewReaderBytes(in_s) read to EOF produces (Break metas
+ * skipped; for a stream that ends in an error, the bytes produced before it), status[s] = EZ_OK or
+ * that first error.  Uses b->in, in_off, out_size (required), status (may be NULL), count and
+ * max_len (host hint: the longest INPUT stream in bytes, 0 = unknown; it picks the chunk size and
+ * nothing else: any value gives the same results).  b->out, out_off, in_bytes, out_bytes are
+ * ignored (out and out_off may be NULL).  workspace >= ez_decompress_workspace(count) enables the
+ * fast kernel (streams it cannot take go to the exact decoder run dry); NULL = exact decoder only.
+ * The fast kernel is a wave per stream, or, for 4,096 streams or more of at most 4 KiB (max_len), a
+ * lane per stream.  Asynchronous on hip_stream; never waits for the stream.  Reads in[0 .. in_off[count]) as
+ * ez_decompress_batch does; writes only out_size[0..count), status[0..count) and the workspace.
+ * Sizes are 64-bit throughout: an output over 4 GiB is reported, not clamped.
+ * Held by tests/test_gpu_k2z.py and tests/test_k2_size.py. */
+int ez_decompressed_size_batch(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
+/* Introspection (tests, tuning): the chunk bytes the fast kernel takes for a max_len hint (host function). */
+int ez_decompressed_size_chunk(uint64_t max_len);
+/* the chunk bytes the last call of this process ran with (0: exact decoder alone; -1: none yet;
+ * 1: the lane-per-stream kernel, which batches of 4,096 streams or more take when max_len says they
+ * are at most 4 KiB each: no chunks) */
+int ez_decompressed_size_chunk_last(void);
 
 /* ---- host-memory batches over several devices (SURVEY §8b device_or_all) ----
  * Streams share no state (writer.go:40-45, reader.go:17-40), so a batch splits into contiguous
