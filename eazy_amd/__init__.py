@@ -186,8 +186,9 @@ def decompress_kernel_last() -> str:
 
 def compress_route_last() -> str:
     """The route the last batch compress of this process took (ez_compress_route_last):
-    's:lean g16 fw40', 's:parse t32', 'l', 'l:k1c', 'x', 'w:pl', 'w:win', 'w:view' (+ '+gtab');
-    '' none yet.  Tests and measurement."""
+    's:lean g16 fw40', 's:parse t32', 'l', 'l:k1c', 'x', 'w:pl', 'w:win', 'w:view' (+ '+gtab'),
+    or the last Writer-handle call: 'hl:lds', 'hl:global', 'hl:batch zero-copy', 'hl:batch staged',
+    'hw:pl', 'hw:view', 'hw:multi' (+ '+gtab'); '' none yet.  Tests and measurement."""
     L = _lib()
     L.ez_compress_route_last.argtypes = [C.c_char_p, C.c_int]
     buf = C.create_string_buffer(64)

@@ -790,6 +790,11 @@ hipError_t launch_general(const CompressArgs &a, hipStream_t st) {
         const bool view = !pl && b.win_bytes == 0;
         if (htl) set_compress_route(pl ? "w:pl" : (view ? "w:view" : "w:win"));
         else set_compress_route(pl ? "w:pl+gtab" : (view ? "w:view+gtab" : "w:win+gtab"));
+    } else if (a.write_idx) {  // a handle's launches: several Writes of one call (the global view, 64-bit positions)
+        set_compress_route(htl ? "hw:multi" : "hw:multi+gtab");
+    } else {  // ... and one Write, staged in LDS or in the global view (a ring has no LDS window)
+        if (htl) set_compress_route(pl ? "hw:pl" : "hw:view");
+        else set_compress_route(pl ? "hw:pl+gtab" : "hw:view+gtab");
     }
     if (pl) {
         if (htl) return ring ? launch_variant<true, true, true>(b, st, lds, g) : launch_variant<true, true, false>(b, st, lds, g);

@@ -161,8 +161,9 @@ hipError_t launch_compress_split(const CompressArgs &a, uint32_t *scratch, hipSt
 // the K1 kernel a batch launch takes: 's' K1s (parse + token writer), 'w' general wave per stream
 char compress_variant(const CompressArgs &a);
 void select_compress_variant(int v);  // 0 = automatic, else a variant letter (tests, A/B)
-// the route of the last batch compress (ez_compress_route_last): every launcher stores the name of
-// what it launched, a string literal; a launcher that calls another one (K1x) stores its own last
+// the route of the last batch compress or Writer-handle call (ez_compress_route_last): every launcher
+// stores the name of what it launched, a string literal; a launcher that calls another one (K1x, a
+// handle call of several K1L Writes) stores its own last.  DESIGN §4 lists the names
 void set_compress_route(const char *route);
 const char *last_compress_route();
 // K1L: the lean parse for long fresh streams (ez_k1_long.hip); resumes K1x's streams (spec_mode 2)

@@ -314,10 +314,12 @@ hipError_t launch_long_ring(const CompressArgs &a, uint8_t *recs, hipStream_t st
     // Writes of up to kLdsWrite bytes: the Write and the ring's last bytes in LDS, the token writer in
     // the same kernel
     if (a.max_len <= (uint64_t)kLdsWrite) {
+        set_compress_route("hl:lds");
         hipLaunchKernelGGL(k1_long_ring<true>, dim3(1), dim3(256), (size_t)a.hs * 4 + kLdsRing + kLdsWrite + 64, st, a, (uint4 *)recs,
                            rcap);
         return hipGetLastError();
     }
+    set_compress_route("hl:global");
     hipLaunchKernelGGL(k1_long_ring<false>, dim3(1), dim3(256), (size_t)a.hs * 4, st, a, (uint4 *)recs, rcap);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -239,6 +239,8 @@ int writer_run_long(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t
         }
         he = ez::launch_long_ring(a, w->recs.as<uint8_t>(), w->stream);
     }
+    // (a single Write's route is its launch's; a call of several says how they reached the device)
+    if (k > 1) ez::set_compress_route(zc ? "hl:batch zero-copy" : "hl:batch staged");
     if (he == hipSuccess && !zc) he = hipMemcpyAsync(H + o_meta, D + o_meta, o_o - o_meta + bound, hipMemcpyDeviceToHost, w->stream);
     bool seen = false;
     if (he == hipSuccess && zc) {

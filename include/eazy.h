@@ -331,7 +331,11 @@ int ez_decompress_kernel_last(void);
  * (k1_lean: lanes per stream, the judgement's forward bytes), "s:parse t32", "s:parse t16 mw"
  * (k1_parse: table width, multi-Write), "l" (K1L), "l:k1c" (K1c, K1L behind it), "x" (K1x),
  * "w:pl" / "w:win" / "w:view" (the general kernel: stream staged in LDS, 32 KiB LDS window, global
- * view), "+gtab" appended when its hash tables are in global scratch. */
+ * view), "+gtab" appended when its hash tables are in global scratch.  A Writer handle's call stores
+ * its route too: "hl:lds" / "hl:global" (K1L on the handle's ring, the Write staged in LDS / read from
+ * global memory), "hl:batch zero-copy" / "hl:batch staged" (several such Writes in one call), "hw:pl" /
+ * "hw:view" / "hw:multi" (the general kernel on the ring: one Write staged in LDS, one in the global
+ * view, several Writes in one launch), "+gtab" appended when the table has more than 4096 entries. */
 int ez_compress_route_last(char *buf, int cap);
 /* Testing: K1c (the chunk-parallel parse of long fresh streams, which proves each stream's parse
  * is Go's or gives it to K1L) counts its verdicts while counting is on: counts (6 words, may be
