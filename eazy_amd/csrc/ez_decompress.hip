@@ -35,6 +35,7 @@ struct Dec {
     // config (reader.go:27-30)
     int64_t limit;
     bool req_magic, skip_meta;
+    bool more;  // b is a window of r.b, which goes on after it
 };
 
 // Reader.reset reader.go:327-344 (the ring is the linear output from here on)
@@ -52,7 +53,10 @@ __device__ int d_continue_meta(Dec &d, int64_t st, int64_t *io) {
     st--;
     int64_t meta, l;
     int err = dec_meta(d.b, d.nb, i, &meta, &l, &i);
-    if (err) { *io = i; return err; }
+    // (reader.go:276-279 returns i, past the meta's first byte, when r.b ends inside the meta's header:
+    // that byte is consumed.  Where only the handle's upload window ends there, nothing is: the next
+    // window starts at the meta)
+    if (err) { *io = d.more && err == EZ_ESHORTBUF ? st : i; return err; }
     if (d.boff == 0 && st == 0 && meta != kMetaMagic && d.req_magic) { *io = st; return EZ_ENOMAGIC; }
     if (i + l > d.nb) { *io = st; return EZ_ESHORTBUF; }
     const int64_t j = meta >> 3;
@@ -192,6 +196,7 @@ __global__ __launch_bounds__(64) void k2_decompress(DecompressArgs A) {
         d.limit = A.block_size_limit;
         d.req_magic = A.require_magic != 0;
         d.skip_meta = A.skip_unsupported_meta != 0;
+        d.more = A.handle && A.more;
         // (the size query, A.dry: no slot -- nothing is stored, and no capacity ends the read)
         uint8_t *out = A.dry ? nullptr : A.out + A.out_off[s];
         const int64_t cap = A.dry ? (int64_t)1 << 62 : (int64_t)(A.out_off[s + 1] - A.out_off[s]);

@@ -109,6 +109,7 @@ struct DecompressArgs {
     int require_magic;
     int skip_unsupported_meta;
     int handle;               // 1 = single streaming call (Reader.Read loop without refill)
+    int more;                 // handle: in is a window of the Reader's buffer, which goes on after it (see d_continue_meta)
     int64_t boff;             // handle: absolute offset of in[0]
     DecodeState *st;          // handle: state in/out
     uint32_t *slow;           // batch: [0] = count, [1..] = streams the fast path handed over (nullptr = exact path only)

@@ -29,7 +29,8 @@ enum { kParseSkip = 0, kParseToken = 1, kParseHandOver = -1 };
 enum { kScanReset = 2 };  // k2_scan only: a MetaReset, valid only before any output
 // k2_scan with partial (a Reader's buffered input, which may end inside a token): the step at i runs
 // past the input's end.  t.adv = 0: its header (or meta) is incomplete, nothing of it is consumed
-// (readTag / continueMetaTag return ErrShortBuffer at i, reader.go:218-325); else a literal whose
+// (readTag / continueMetaTag return ErrShortBuffer at i, reader.go:218-325; but for a meta's first byte
+// alone, which the Reader has consumed: stream_ahead in ez_reader.hip sees to that); else a literal whose
 // header is whole and whose body runs past the end (read copies the bytes there are, :166-168)
 enum { kScanTail = 3 };
 

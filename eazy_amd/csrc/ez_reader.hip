@@ -433,7 +433,10 @@ int stream_ahead(ez_reader *r, const uint8_t *b, size_t b_len, size_t i, int64_t
         r->a_at = 0;
         r->brk_next = 0;
         r->stage_at = r->stage_n = 0;
-        r->s_iend = boff + (int64_t)(n2 == 0 || tj > 0 ? b_len : i + k + (size_t)stop);
+        // (a meta's first byte alone at the input's end: the Reader consumes it before it misses the
+        // second, reader.go:276-279, so a stream that ends there ends clean and the next input starts a token)
+        const bool lone = n2 && tj == 0 && stop == (int64_t)n2 - 1 && b[b_len - 1] == ez::kMeta;
+        r->s_iend = boff + (int64_t)(n2 == 0 || tj > 0 || lone ? b_len : i + k + (size_t)stop);
         r->s_on = 1;
         r->s_count++;
         return 1;
@@ -470,7 +473,8 @@ void ez::reader_release_cached(int dev) {
 // Input is uploaded in windows from b[i] on, not the whole of b per call: a Read loop over one large
 // NewReaderBytes buffer then moves each input byte to the device about once.  A window that ends inside
 // a token makes the decoder stop there with EZ_ESHORTBUF and nothing of that token consumed
-// (reader.go:218-270), so the next window resumes at exactly that token; a token longer than the window
+// (reader.go:218-270; DecompressArgs.more, for the one byte the Reader would consume, a meta's first),
+// so the next window resumes at exactly that token; a token longer than the window
 // with no progress doubles the window.  The decoded block history sits in front of the output in one of
 // two device buffers; after a call the last min(pos, bs) bytes are copied once into the head of the
 // other buffer, which the next call decodes into.
@@ -523,6 +527,7 @@ extern "C" int ez_reader_read(ez_reader *r, const uint8_t *b, size_t b_len, size
         a.require_magic = r->require_magic;
         a.skip_unsupported_meta = r->skip_meta;
         a.handle = 1;
+        a.more = take < b_len - at;   // the window ends before the input does
         a.boff = boff + (int64_t)at;  // absolute offset of the window's first byte
         a.st = r->dstate.as<ez::DecodeState>();
         EZ_HIP(ez::launch_decompress(a, r->stream));
