@@ -188,7 +188,8 @@ def compress_route_last() -> str:
     """The route the last batch compress of this process took (ez_compress_route_last):
     's:lean g16 fw40', 's:parse t32', 'l', 'l:k1c', 'x', 'w:pl', 'w:win', 'w:view' (+ '+gtab'),
     or the last Writer-handle call: 'hl:lds', 'hl:global', 'hl:batch zero-copy', 'hl:batch staged',
-    'hw:pl', 'hw:view', 'hw:multi' (+ '+gtab'); '' none yet.  Tests and measurement."""
+    'hw:pl', 'hw:view', 'hw:multi' (+ '+gtab'), or write_many's 'hm:lds', 'hm:lds+own', 'hm:own';
+    '' none yet.  Tests and measurement."""
     L = _lib()
     L.ez_compress_route_last.argtypes = [C.c_char_p, C.c_int]
     buf = C.create_string_buffer(64)
@@ -452,6 +453,56 @@ class Writer:
 
 def NewWriter(wr, block: int, htable: int, device: int = 0) -> Writer:
     return Writer(wr, block, htable, device)
+
+
+def write_many(writers, ps) -> list:
+    """One Write on each of several Writers in one device call (ez_writer_write_many; no
+    reference counterpart: many live streams that each receive a small Write at about the same
+    time).  Every sink sees exactly what ``writers[j].Write(ps[j])`` would give it, in order: each
+    Writer's w.b gets its bytes and its FlushThreshold is applied.  The Writers are distinct and on
+    one device; they need not share sizes, AppendMagic or state.  A failed Writer restarts its
+    stream as after Write; the others' bytes are delivered, then the first error (a Write's or a
+    sink's) is raised.  Returns the bytes each Write took."""
+    writers = list(writers)
+    ps = [bytes(p) for p in ps]
+    k = len(ps)
+    if len(writers) != k:
+        raise ValueError("write_many: one Write per Writer")
+    if k == 0:
+        return []
+    L = _lib()
+    L.ez_writer_write_many.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p]
+    hs = (C.c_void_p * k)(*[w._h for w in writers])
+    ends = (C.c_uint64 * k)()
+    at = 0
+    for j, p in enumerate(ps):
+        at += len(p)
+        ends[j] = at
+    cap = sum(compress_bound(len(p)) for p in ps)
+    buf = (C.c_uint8 * max(cap, 1))()
+    oe = (C.c_uint64 * k)()
+    st = (C.c_int32 * k)(*([-1] * k))
+    code = L.ez_writer_write_many(hs, k, b"".join(ps), ends, buf, cap, oe, st)
+    if code != OK and st[0] == -1:  # the call was refused: no handle has changed
+        _check(code)
+    out = C.string_at(buf, oe[k - 1])
+    first, prev = None, 0
+    for j, w in enumerate(writers):
+        try:
+            if st[j] != OK:
+                try:
+                    _check(st[j])
+                except EazyError as e:
+                    raise w._failed(e) from None
+            w._b += out[prev : oe[j]]
+            w._write()
+        except Exception as e:  # noqa: BLE001 - the other Writers' bytes are delivered first
+            first = first or e
+        prev = oe[j]
+    if first is not None:
+        raise first
+    return [len(p) for p in ps]
 
 
 # ---------------------------------------------------------------- Reader

@@ -37,7 +37,9 @@
 #include <memory>
 #include <tuple>
 #include <stdexcept>
+#include <exception>
 #include <string>
+#include <string_view>
 #include <utility>
 #include <vector>
 
@@ -263,6 +265,7 @@ class Writer {
     }
 
   private:
+    friend std::pair<std::vector<size_t>, Err> WriteMany(std::vector<Writer *> &, const std::vector<std::string_view> &);
     ez_writer *h_ = nullptr;
     std::vector<uint8_t> b_;  // w.b
     int64_t written_ = 0;     // w.written
@@ -322,6 +325,58 @@ class Writer {
 
 inline std::unique_ptr<Writer> NewWriter(IoWriter *w, int64_t block, int64_t htable, int device = 0) {
     return std::make_unique<Writer>(w, block, htable, device);
+}
+
+// One Write on each of several Writers in one device call (ez_writer_write_many; no reference
+// counterpart): every sink sees what ws[j]->Write(ps[j]) would give it, in order.  The Writers are
+// distinct and on one device.  A failed Writer restarts its stream as after Write; the others' bytes
+// are delivered first.  {the bytes each Write took (0 for a failed one), the first error}; a call the
+// library refuses (a Writer named twice, different devices) throws std::invalid_argument, as does a
+// failed Write with invalid arguments or a reference panic behind it, after the others' delivery.
+inline std::pair<std::vector<size_t>, Err> WriteMany(std::vector<Writer *> &ws, const std::vector<std::string_view> &ps) {
+    const size_t k = ps.size();
+    if (ws.size() != k) throw std::invalid_argument("eazy: WriteMany: one Write per Writer");
+    std::vector<size_t> took(k, 0);
+    if (k == 0) return {took, Err::OK};
+    std::vector<ez_writer *> hs(k);
+    std::vector<uint64_t> ends(k), oe(k);
+    std::vector<int32_t> st(k, -1);
+    std::string in;
+    size_t cap = 0;
+    for (size_t j = 0; j < k; j++) {
+        if (!ws[j]) throw std::invalid_argument("eazy: WriteMany: null Writer");
+        ws[j]->sync();
+        hs[j] = ws[j]->h_;
+        in.append(ps[j]);
+        ends[j] = in.size();
+        cap += ez_compress_bound(ps[j].size());
+    }
+    std::vector<uint8_t> tmp(cap ? cap : 1);
+    const int rc = ez_writer_write_many(hs.data(), k, (const uint8_t *)in.data(), ends.data(), tmp.data(), cap, oe.data(), st.data());
+    if (rc != EZ_OK && st[0] == -1) {  // the call was refused: no handle has changed
+        if (rc == EZ_EINVAL) throw std::invalid_argument("eazy: WriteMany: invalid arguments");
+        return {took, (Err)rc};
+    }
+    Err first = Err::OK;
+    std::exception_ptr thrown;
+    for (size_t j = 0, prev = 0; j < k; prev = (size_t)oe[j], j++) {
+        Err e = Err::OK;
+        try {
+            if (st[j] != EZ_OK) {
+                e = ws[j]->failed(st[j]);
+            } else {
+                ws[j]->b_.insert(ws[j]->b_.end(), tmp.begin() + (ptrdiff_t)prev, tmp.begin() + (ptrdiff_t)oe[j]);
+                e = ws[j]->write();
+            }
+        } catch (...) {
+            if (!thrown && first == Err::OK) thrown = std::current_exception();
+            continue;
+        }
+        if (e == Err::OK) took[j] = ps[j].size();
+        else if (first == Err::OK && !thrown) first = e;
+    }
+    if (thrown) std::rethrow_exception(thrown);
+    return {took, first};
 }
 
 // ---------------------------------------------------------------- Reader

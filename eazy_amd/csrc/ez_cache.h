@@ -40,10 +40,28 @@ struct CacheEntry {
         cap = c;
         return true;
     }
+    // pinned host staging beside it, for a call that copies through the entry (ez_writer_write_many):
+    // grow-only as p is; false when the allocation fails
+    void *hp = nullptr;
+    size_t hcap = 0;
+    bool ensure_host(size_t n) {
+        if (n <= hcap) return true;
+        if (hp) (void)hipHostFree(hp);
+        hp = nullptr;
+        hcap = 0;
+        const size_t c = n < 65536 ? 65536 : n + n / 4;
+        if (hipHostMalloc(&hp, c, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        hcap = c;
+        return true;
+    }
     void release() {
         if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        if (hp) (void)hipHostFree(hp);
+        p = hp = nullptr;
+        cap = hcap = 0;
     }
 };
 

@@ -307,8 +307,8 @@ extern "C" int ez_decompressed_size_chunk_last(void) { return ez::last_size_chun
 
 // Frees the device scratch the batch calls keep between calls (no reference counterpart; like a
 // caching allocator's empty_cache): the K1 / K1c scratch and K2j workspaces per (device, HIP stream),
-// the multi-device calls' pooled shard buffers and the Reader handles' shared K2j workspace, on
-// `device` (< 0: every device).  Scratch a call is using at that moment is kept.
+// the multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace and
+// ez_writer_write_many's staging, on `device` (< 0: every device).  Scratch a call is using at that moment is kept.
 extern "C" int ez_release_cached(int device) {
     const int have = device_count();
     if (have <= 0) return EZ_EDEVICE;
@@ -319,6 +319,7 @@ extern "C" int ez_release_cached(int device) {
         k1_cache().trim(d);
         ez::jump_cache().trim(d);
         reader_release_cached(d);
+        writer_release_cached(d);
     }
     multi_release_cached(device);
     return EZ_OK;

@@ -16,6 +16,7 @@ int device_count();  // (ez_capi.hip; 0 when the runtime reports none)
 // ez_release_cached's part in the file that owns the scratch; the caller's thread is bound to dev
 void reader_release_cached(int dev);    // the Readers' shared K2j workspace of dev, unless one is using it
 void multi_release_cached(int device);  // the idle shard buffers of device (< 0: every device)
+void writer_release_cached(int dev);    // ez_writer_write_many's idle staging, device buffers and records of dev
 
 struct DeviceGuard {
     int prev = -1;

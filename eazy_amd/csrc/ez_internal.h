@@ -178,6 +178,18 @@ bool long_ring_applies(const CompressArgs &a);
 constexpr uint64_t kHandleLdsWrite = 49152;
 uint64_t long_ring_scratch_bytes(const CompressArgs &a);
 hipError_t launch_long_ring(const CompressArgs &a, uint8_t *recs, hipStream_t s);
+// K1L on one Write of each of many handles in one launch (ez_writer_write_many): what block b needs
+// of handle b's CompressArgs, in device memory; its in_off[2] out_off[2] out_size status words are
+// the b-th six of the launch's meta words
+struct RingDesc {
+    uint8_t *ring;
+    uint32_t *ht;
+    int64_t bs, hs, start;
+    int32_t header, append_magic;
+};
+uint64_t long_rings_scratch_bytes(uint64_t count, uint64_t longest);
+hipError_t launch_long_rings(uint8_t *D, uint64_t *meta, const RingDesc *desc, uint64_t count, int64_t max_hs, uint64_t longest,
+                             uint8_t *recs, hipStream_t s);
 bool compress_forced_general();  // ez_select_compress_kernel('w') (tests, A/B)
 bool compress_forced_long();     // ez_select_compress_kernel('l'): K1L alone, without K1c (tests, A/B)
 // K1c (chunk-parallel K1L, ez_k1_chunk.hip): counting of its verdicts (ez_compress_k1c_stats)

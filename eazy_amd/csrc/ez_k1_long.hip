@@ -1,5 +1,6 @@
 // ez_k1_long.hip — K1L's kernels and launchers: k1_long (long fresh streams of a batch, and the
-// streams K1x or K1c hand over) and k1_long_ring / k1_ring_store (one Write on a Writer handle).
+// streams K1x or K1c hand over), k1_long_ring / k1_ring_store (one Write on a Writer handle) and
+// k1_long_rings (one Write on each of many handles).
 // The parse loop itself is ez_k1_long.h's long_loop.
 #include "ez_k1_long.h"
 #include "ez_k1_emit.h"
@@ -152,8 +153,10 @@ __device__ __forceinline__ int32_t knob_dev_rl(int32_t n) {
     const int32_t r = 16 * n < EZ_K1R_RL ? EZ_K1R_RL : (16 * n > kLdsRing ? kLdsRing : ((16 * n + 15) & ~15));
     return r > kLdsRing ? kLdsRing : r;
 }
+// one Write on one handle by one 256-thread block: k1_long_ring's whole work (A: the handle's args,
+// count 1; recs: the block's rcap records)
 template <bool LDS>
-__global__ __launch_bounds__(256) void k1_long_ring(CompressArgs A, uint4 *recs, uint64_t rcap) {
+__device__ __forceinline__ void long_ring_block(const CompressArgs &A, uint4 *recs, uint64_t rcap) {
     constexpr int G = 16;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = (int)threadIdx.x, lane = tid & 63;  // 4 waves stage; wave 0's first group parses
@@ -237,6 +240,39 @@ __global__ __launch_bounds__(256) void k1_long_ring(CompressArgs A, uint4 *recs,
             }
         }
     }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void k1_long_ring(CompressArgs A, uint4 *recs, uint64_t rcap) {
+    long_ring_block<LDS>(A, recs, rcap);
+}
+
+// One Write on each of gridDim.x handles (ez_writer_write_many): block b is k1_long_ring<true> for
+// handle b, whose ring, table and sizes it reads from desc[b] and whose in_off[2] out_off[2] out_size
+// status words are meta[6 b ..]; offsets count from D, the call's staging buffer.  The blocks share
+// nothing: each has its own handle (the host refuses a handle named twice), meta words, output slot
+// and rcap records.  The LDS layout is the one-handle kernel's with this block's own table size.
+__global__ __launch_bounds__(256) void k1_long_rings(uint8_t *D, uint64_t *meta, const RingDesc *desc, uint4 *recs, uint64_t rcap) {
+    const RingDesc d = desc[blockIdx.x];
+    uint64_t *m = meta + 6 * (uint64_t)blockIdx.x;
+    CompressArgs A{};
+    A.in = D;
+    A.in_off = m;
+    A.out = D;
+    A.out_off = m + 2;
+    A.out_size = m + 4;
+    A.status = (int32_t *)(m + 5);
+    A.count = 1;
+    A.bs = d.bs;
+    A.hs = d.hs;
+    A.append_magic = d.append_magic;
+    A.ver = 0;
+    A.header = d.header;
+    A.start = d.start;
+    A.ring = d.ring;
+    A.ht_global = d.ht;
+    A.max_len = m[1] - m[0];
+    long_ring_block<true>(A, recs + (uint64_t)blockIdx.x * rcap, rcap);
 }
 
 // the Write's last min(n, bs) bytes into the handle's ring (block[(start + k) & mask], copyData)
@@ -327,6 +363,25 @@ hipError_t launch_long_ring(const CompressArgs &a, uint8_t *recs, hipStream_t st
     const uint64_t n = a.max_len;
     const uint64_t blocks = (n < (uint64_t)a.bs ? n : (uint64_t)a.bs) / 256 / 16 + 1;
     hipLaunchKernelGGL(k1_ring_store, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// K1L for one Write on each of `count` handles in one launch (ez_writer_write_many): Writes of 16 ..
+// kLdsWrite bytes that long_ring_applies holds for, the longest of `longest` bytes, on tables of at
+// most max_hs entries.  D, meta and desc as k1_long_rings reads them; recs: long_rings_scratch_bytes
+uint64_t long_rings_rcap(uint64_t longest) { return longest / 6 + 1; }
+uint64_t long_rings_scratch_bytes(uint64_t count, uint64_t longest) { return count * long_rings_rcap(longest) * sizeof(WideRec); }
+hipError_t launch_long_rings(uint8_t *D, uint64_t *meta, const RingDesc *desc, uint64_t count, int64_t max_hs, uint64_t longest,
+                             uint8_t *recs, hipStream_t st) {
+    if (count == 0 || count > 0x7fffffffull || longest > (uint64_t)kLdsWrite || max_hs > 4096) return hipErrorInvalidValue;
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute((const void *)k1_long_rings, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_done = true;
+    }
+    // (the staging loop stores whole 16-byte pieces: the Write's length rounded up)
+    const size_t lds = (size_t)max_hs * 4 + kLdsRing + (((size_t)longest + 15) & ~(size_t)15) + 64;
+    hipLaunchKernelGGL(k1_long_rings, dim3((unsigned)count), dim3(256), lds, st, D, meta, desc, (uint4 *)recs, long_rings_rcap(longest));
     return hipGetLastError();
 }
 

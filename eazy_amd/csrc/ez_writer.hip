@@ -4,8 +4,12 @@
 
 #include <string.h>
 
+#include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <vector>
 
+#include "ez_cache.h"
 #include "ez_format.h"
 #include "ez_host.h"
 #include "ez_internal.h"
@@ -155,6 +159,27 @@ ez::CompressArgs long_args(const ez_writer *w, uint8_t *D, uint64_t *dm, const u
     return handle_args(w, D, dm, w->pristine && j == 0, w->pos + (int64_t)write_start(ends, j), write_len(ends, j));
 }
 
+// One Write's meta block, six words a launch reads and writes: the Write at [in0, in1) of the staging
+// buffer, its output slot of b bytes at o, and the size and status the kernels store
+constexpr size_t kMetaWords = 6;
+void meta_fill(uint64_t *mj, uint64_t in0, uint64_t in1, uint64_t o, uint64_t b) {
+    mj[0] = in0;
+    mj[1] = in1;
+    mj[2] = o;
+    mj[3] = o + b;
+    mj[4] = 0;
+    mj[5] = 0;
+}
+size_t meta_size(const uint64_t *mj) { return (size_t)mj[4]; }
+int meta_status(const uint64_t *mj) { return (int)(int32_t)(mj[5] & 0xffffffffu); }
+
+// n bytes of Writes have succeeded: the handle's stream goes on after them
+void writer_advance(ez_writer *w, size_t n) {
+    w->pos += (int64_t)n;
+    w->pristine = false;
+    w->tainted = false;
+}
+
 // Writes that failed after their launch (st: the kernel's status, or EZ_EDEVICE).  The device history
 // may already hold p while the stream position does not: start the stream over, as Go does after a
 // failed sink write (writer.go:391-393), so later Writes stay exact.  Returns the call's error.
@@ -191,7 +216,7 @@ int writer_run_long(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t
     }
     // [input | per Write: in_off[2] out_off[2] out_size status | outputs, Write j's at its bound prefix]
     const size_t o_meta = (n + 15) & ~(size_t)15;
-    const size_t o_o = (o_meta + 6 * 8 * k + 15) & ~(size_t)15;
+    const size_t o_o = (o_meta + kMetaWords * 8 * k + 15) & ~(size_t)15;
     const size_t o_flag = (o_o + bound + 16 + 63) & ~(size_t)63;  // the completion flag (zero-copy path)
     const size_t total = o_flag + 64;
     // Writes K1L stages in LDS (read once): the kernels read them, and write the output, in the pinned
@@ -216,23 +241,17 @@ int writer_run_long(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t
     size_t boff = 0;
     for (size_t j = 0; j < k; j++) {
         const size_t b = ez_compress_bound((size_t)write_len(ends, j));
-        uint64_t *mj = m + 6 * j;
-        mj[0] = write_start(ends, j);
-        mj[1] = ends[j];
-        mj[2] = o_o + boff;
-        mj[3] = o_o + boff + b;
-        mj[4] = 0;
-        mj[5] = 0;
+        meta_fill(m + kMetaWords * j, write_start(ends, j), ends[j], o_o + boff, b);
         boff += b;
     }
-    if (!zc) EZ_HIP(hipMemcpyAsync(D, H, o_meta + 6 * 8 * k, hipMemcpyHostToDevice, w->stream));
+    if (!zc) EZ_HIP(hipMemcpyAsync(D, H, o_meta + kMetaWords * 8 * k, hipMemcpyHostToDevice, w->stream));
     w->tainted = true;  // (cleared when the call completes, or by the reset of a failed one)
     hipError_t he = hipSuccess;
     volatile uint32_t *flag = (volatile uint32_t *)(H + o_flag);
     const uint32_t seq = ++w->seq;
     *flag = seq + 1;  // (not the value this call waits for, whatever the buffer held)
     for (size_t j = 0; j < k && he == hipSuccess; j++) {
-        ez::CompressArgs a = long_args(w, D, (uint64_t *)(D + o_meta) + 6 * j, ends, j);
+        ez::CompressArgs a = long_args(w, D, (uint64_t *)(D + o_meta) + kMetaWords * j, ends, j);
         if (zc && j + 1 == k) {  // the last Write's kernel signals its end in the pinned buffer
             a.done_flag = (uint32_t *)(D + o_flag);
             a.done_seq = seq;
@@ -255,21 +274,19 @@ int writer_run_long(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t
     int st = EZ_OK;
     size_t got = 0;
     for (size_t j = 0; j < k && !st; j++) {
-        st = (int)(int32_t)(m[6 * j + 5] & 0xffffffffu);
-        got += (size_t)m[6 * j + 4];
+        st = meta_status(m + kMetaWords * j);
+        got += meta_size(m + kMetaWords * j);
     }
     if (!st && got > cap) st = EZ_ENOSPC;  // cannot happen (cap >= the sum of the bounds)
     if (st) return writer_fail(w, st, ends, k);
     size_t at = 0;
     for (size_t j = 0; j < k; j++) {
-        const size_t sz = (size_t)m[6 * j + 4];
-        if (sz) memcpy(out + at, H + (size_t)m[6 * j + 2], sz);
+        const size_t sz = meta_size(m + kMetaWords * j);
+        if (sz) memcpy(out + at, H + (size_t)m[kMetaWords * j + 2], sz);
         at += sz;
         if (out_ends) out_ends[j] = at;
     }
-    w->pos += (int64_t)n;
-    w->pristine = false;
-    w->tainted = false;
+    writer_advance(w, n);
     return EZ_OK;
 }
 
@@ -309,7 +326,8 @@ int writer_run(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t k, u
     uint8_t *H = w->host.as<uint8_t>(), *D = w->dev.as<uint8_t>();
     if (n) memcpy(H, p, n);
     uint64_t *m = (uint64_t *)(H + o_meta);
-    m[0] = 0; m[1] = n; m[2] = o_o; m[3] = o_o + bound; m[4] = 0; m[5] = 0; m[6] = 0; m[7] = k;
+    meta_fill(m, 0, n, o_o, bound);
+    m[6] = 0; m[7] = k;
     for (size_t j = 0; j < k; j++) m[8 + j] = ends[j];
     EZ_HIP(hipMemcpyAsync(D, H, o_meta + nm * 8, hipMemcpyHostToDevice, w->stream));
     uint64_t *dm = (uint64_t *)(D + o_meta);
@@ -329,8 +347,8 @@ int writer_run(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t k, u
         he = hipMemcpyAsync(H + o_meta, D + o_meta, o_o - o_meta + bound, hipMemcpyDeviceToHost, w->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(w->stream);
     if (he != hipSuccess) return writer_fail(w, EZ_EDEVICE, ends, k);
-    int st = (int)(int32_t)(m[5] & 0xffffffffu);
-    const size_t got = (size_t)m[4];
+    int st = meta_status(m);
+    const size_t got = meta_size(m);
     if (!st && got > bound) st = EZ_ENOSPC;  // cannot happen (tests/test_bound.py)
     if (st) return writer_fail(w, st, ends, k);
     if (got) memcpy(out, H + o_o, got);
@@ -338,13 +356,27 @@ int writer_run(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t k, u
         if (k > 1) for (size_t j = 0; j < k; j++) out_ends[j] = m[8 + k + j];
         else if (k == 1) out_ends[0] = got;
     }
-    w->pos += (int64_t)n;
-    w->pristine = false;
-    w->tainted = false;
+    writer_advance(w, n);
     return EZ_OK;
 }
 
+// ez_writer_write_many's staging, device buffer and records per (device, HIP stream), leased for the call
+ez::DevCache &many_cache() {
+    static ez::DevCache *c = new ez::DevCache();  // (never destroyed: no hipFree after the runtime's teardown)
+    return *c;
+}
+std::atomic<uint64_t> g_many_shared{0}, g_many_own{0};  // ez_writer_write_many_last
+
+// Whether handle w's next Write, of n bytes, can share ez_writer_write_many's launch: K1L takes it
+// (ez::long_ring_applies) on its LDS path.  a: the Write's args (no buffers yet)
+bool many_shares(const ez_writer *w, uint64_t n, ez::CompressArgs &a) {
+    a = long_args(w, nullptr, nullptr, &n, 0);
+    return !ez::compress_forced_general() && ez::long_ring_applies(a) && n <= ez::kHandleLdsWrite;
+}
+
 }  // namespace
+
+void ez::writer_release_cached(int dev) { many_cache().trim(dev); }
 
 extern "C" int ez_writer_write(ez_writer *w, const uint8_t *p, size_t n, uint8_t *out, size_t cap, size_t *out_n) {
     *out_n = 0;
@@ -360,6 +392,138 @@ extern "C" int ez_writer_write_batch(ez_writer *w, const uint8_t *p, const uint6
     if (k == 0) return EZ_OK;
     if (!ends || !out_ends) return EZ_EINVAL;
     return writer_run(w, p, ends, k, out, cap, out_ends);
+}
+
+// One Write on each of `count` handles.  The Writes K1L takes on its LDS path (many_shares) share one
+// launch, a block per handle (ez::launch_long_rings), through one leased staging buffer:
+// [those Writes | per handle: in_off[2] out_off[2] out_size status | descriptors | outputs at their bound
+// prefixes], one host->device copy, one device->host copy and one synchronisation on the first handle's
+// HIP stream (every handle's own stream is idle: each handle call ends synchronised).  Every other Write
+// then runs as ez_writer_write does (writer_run); the bytes reach `out` in handle order.
+extern "C" int ez_writer_write_many(ez_writer *const *w, size_t count, const uint8_t *p, const uint64_t *ends, uint8_t *out,
+                                    size_t cap, uint64_t *out_ends, int32_t *status) {
+    if (count == 0) {
+        g_many_shared = g_many_own = 0;
+        return EZ_OK;
+    }
+    // the call's refusals, before anything reaches a device or a handle
+    if (!w || !ends || !out_ends) return EZ_EINVAL;
+    size_t bound = 0;
+    for (size_t j = 0; j < count; j++) {
+        if (!w[j] || ends[j] < write_start(ends, j) || w[j]->device != w[0]->device) return EZ_EINVAL;
+        bound += ez_compress_bound((size_t)write_len(ends, j));
+    }
+    {
+        std::vector<const ez_writer *> s(w, w + count);
+        std::sort(s.begin(), s.end());
+        if (std::adjacent_find(s.begin(), s.end()) != s.end()) return EZ_EINVAL;
+    }
+    if (cap < bound) return EZ_ENOSPC;
+    DeviceGuard g(w[0]->device);
+    if (!g.ok) return EZ_EDEVICE;
+    hipStream_t stream = w[0]->stream;
+
+    std::vector<int> st(count, EZ_OK);
+    std::vector<size_t> shared;  // the handles of the shared launch, in order
+    std::vector<ez::RingDesc> desc;
+    uint64_t longest = 0;
+    int64_t max_hs = 0;
+    size_t nin = 0, sbound = 0;
+    for (size_t j = 0; j < count; j++) {
+        w[j]->last_panic = EZ_PANIC_NONE;
+        if ((st[j] = writer_clean(w[j])) != EZ_OK) continue;
+        const uint64_t n = write_len(ends, j);
+        ez::CompressArgs a;
+        if (!many_shares(w[j], n, a)) continue;
+        shared.push_back(j);
+        desc.push_back(ez::RingDesc{a.ring, a.ht_global, a.bs, a.hs, a.start, a.header, a.append_magic});
+        longest = n > longest ? n : longest;
+        max_hs = a.hs > max_hs ? a.hs : max_hs;
+        nin += (size_t)n;
+        sbound += ez_compress_bound((size_t)n);
+    }
+
+    ez::CacheLease lease;
+    const size_t ns = shared.size();
+    const size_t o_meta = (nin + 15) & ~(size_t)15;
+    const size_t o_desc = o_meta + kMetaWords * 8 * ns;
+    const size_t o_o = (o_desc + sizeof(ez::RingDesc) * ns + 15) & ~(size_t)15;
+    const size_t total = (o_o + sbound + 16 + 255) & ~(size_t)255;  // (the records after it)
+    uint8_t *H = nullptr;
+    if (ns) {
+        lease = many_cache().acquire(w[0]->device, (void *)stream);
+        if (!lease->ensure(total + (size_t)ez::long_rings_scratch_bytes(ns, longest)) || !lease->ensure_host(total))
+            return EZ_EDEVICE;  // (no handle has been touched)
+        H = (uint8_t *)lease->hp;
+        uint8_t *D = (uint8_t *)lease->p;
+        uint64_t *m = (uint64_t *)(H + o_meta);
+        size_t ioff = 0, boff = 0;
+        for (size_t s = 0; s < ns; s++) {
+            const size_t j = shared[s], n = (size_t)write_len(ends, j), b = ez_compress_bound(n);
+            memcpy(H + ioff, p + write_start(ends, j), n);
+            meta_fill(m + kMetaWords * s, ioff, ioff + n, o_o + boff, b);
+            ioff += n;
+            boff += b;
+            // from the launch on, the handle's ring and table may hold the Write (cleared by writer_advance,
+            // or by the reset of a failed Write)
+            w[j]->tainted = true;
+        }
+        memcpy(H + o_desc, desc.data(), sizeof(ez::RingDesc) * ns);
+        hipError_t he = hipMemcpyAsync(D, H, o_o, hipMemcpyHostToDevice, stream);
+        if (he == hipSuccess)
+            he = ez::launch_long_rings(D, (uint64_t *)(D + o_meta), (const ez::RingDesc *)(D + o_desc), ns, max_hs, longest, D + total,
+                                       stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(H + o_meta, D + o_meta, o_o - o_meta + sbound, hipMemcpyDeviceToHost, stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(stream);
+        if (he != hipSuccess) {  // every handle of the launch fails, and restarts its stream
+            for (size_t s = 0; s < ns; s++) {
+                const uint64_t n = write_len(ends, shared[s]);
+                st[shared[s]] = writer_fail(w[shared[s]], EZ_EDEVICE, &n, 1);
+            }
+        }
+    }
+
+    // in handle order: the shared launch's bytes from the staging buffer, the other Writes now
+    size_t at = 0, s = 0, own = 0;
+    int first = EZ_OK;
+    for (size_t j = 0; j < count; j++) {
+        const uint64_t n = write_len(ends, j);
+        const bool in_launch = s < ns && shared[s] == j;
+        int e = st[j];
+        size_t sz = 0;
+        if (!e && in_launch) {
+            const uint64_t *mj = (const uint64_t *)(H + o_meta) + kMetaWords * s;
+            e = meta_status(mj);
+            sz = meta_size(mj);
+            if (!e && sz > (size_t)(mj[3] - mj[2])) e = EZ_ENOSPC;  // cannot happen (tests/test_bound.py)
+            if (e) {
+                e = writer_fail(w[j], e, &n, 1);
+            } else {
+                if (sz) memcpy(out + at, H + (size_t)mj[2], sz);
+                writer_advance(w[j], (size_t)n);
+            }
+        } else if (!e) {
+            uint64_t oe = 0;
+            e = writer_run(w[j], p + write_start(ends, j), &n, 1, out + at, cap - at, &oe);
+            sz = (size_t)oe;
+            own++;
+        }
+        s += in_launch;
+        if (!e) at += sz;
+        out_ends[j] = at;
+        if (status) status[j] = e;
+        if (e && !first) first = e;
+    }
+    g_many_shared = ns;
+    g_many_own = own;
+    ez::set_compress_route(own == 0 ? "hm:lds" : (ns == 0 ? "hm:own" : "hm:lds+own"));
+    return first;
+}
+
+extern "C" int ez_writer_write_many_last(uint64_t counts[2]) {
+    counts[0] = g_many_shared;
+    counts[1] = g_many_own;
+    return EZ_OK;
 }
 
 extern "C" int ez_writer_header(ez_writer *w, uint8_t *out, size_t cap, size_t *out_n) {

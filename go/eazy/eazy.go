@@ -332,6 +332,66 @@ func (w *Writer) WriteBatch(ps [][]byte) (int, error) {
 	return done, nil
 }
 
+// WriteMany sends one Write to each of several Writers in one device call (no reference
+// counterpart: many live streams that each receive a small Write at about the same time).  Every
+// sink sees what ws[j].Write(ps[j]) would give it, in order.  The Writers are distinct and on one
+// device; they need not share sizes, AppendMagic or state.  A failed Writer restarts its stream as
+// after Write; the others' bytes are delivered, and the first error is returned with the bytes each
+// Write took (0 for a failed one).
+func WriteMany(ws []*Writer, ps [][]byte) ([]int, error) {
+	if len(ws) != len(ps) {
+		return nil, errors.New("eazy: WriteMany: one Write per Writer")
+	}
+	took := make([]int, len(ps))
+	if len(ps) == 0 {
+		return took, nil
+	}
+	var data []byte
+	hs := make([]*C.ez_writer, len(ps))
+	ends := make([]uint64, len(ps))
+	need := 0
+	for j, p := range ps {
+		ws[j].sync()
+		hs[j] = ws[j].h
+		data = append(data, p...)
+		ends[j] = uint64(len(data))
+		need += int(C.ez_compress_bound(C.size_t(len(p))))
+	}
+	out := make([]byte, need+1)
+	oe := make([]uint64, len(ps))
+	st := make([]int32, len(ps))
+	for j := range st {
+		st[j] = -1
+	}
+	rc := C.ez_writer_write_many(&hs[0], C.size_t(len(ps)), ptr(data), (*C.uint64_t)(unsafe.Pointer(&ends[0])),
+		ptr(out), C.size_t(need), (*C.uint64_t)(unsafe.Pointer(&oe[0])), (*C.int32_t)(unsafe.Pointer(&st[0])))
+	runtime.KeepAlive(ws)
+	if rc != C.EZ_OK && st[0] == -1 { // the call was refused: no handle has changed
+		if rc == C.EZ_EINVAL {
+			return took, errors.New("eazy: invalid WriteMany arguments")
+		}
+		return took, toErr(rc, 0)
+	}
+	var first error
+	prev := uint64(0)
+	for j, w := range ws {
+		var err error
+		if st[j] != C.EZ_OK {
+			err = w.failed(C.int(st[j]))
+		} else {
+			w.b = append(w.b, out[prev:oe[j]]...)
+			err = w.write()
+		}
+		prev = oe[j]
+		if err == nil {
+			took[j] = len(ps[j])
+		} else if first == nil {
+			first = err
+		}
+	}
+	return took, first
+}
+
 func (w *Writer) isreset() bool { return int(w.written)+len(w.b) == 0 }
 
 func (w *Writer) write() error { // writer.go:379-385

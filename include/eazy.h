@@ -123,6 +123,25 @@ int ez_writer_write(ez_writer *w, const uint8_t *p, size_t n, uint8_t *out, size
  * ez_writer_write (the stream restarts). */
 int ez_writer_write_batch(ez_writer *w, const uint8_t *p, const uint64_t *ends, size_t k, uint8_t *out, size_t cap,
                           uint64_t *out_ends);
+/* One Write on each of `count` distinct handles in one device call: the same bytes, handle states and
+ * errors as ez_writer_write(w[j], ...) for j = 0 .. count-1.  p holds the Writes back to back, handle j's
+ * ending at p[ends[j]]; out receives their bytes back to back, handle j's ending at out[out_ends[j]].
+ * cap >= the sum of ez_compress_bound(len of Write j).  status (may be NULL) gets EZ_* per handle.
+ * Returns EZ_OK when every Write succeeded, else the first failing handle's code.  A handle whose Write
+ * fails restarts its stream as after ez_writer_write and contributes no bytes (out_ends[j] ==
+ * out_ends[j-1]); the others keep their results.  Refused before anything reaches a device, every
+ * handle as it was: EZ_EINVAL for a NULL w, ends or out_ends, a NULL handle, decreasing ends, a handle
+ * named twice or handles on different devices; EZ_ENOSPC for cap below the sum of the bounds.  count ==
+ * 0 returns EZ_OK.  The handles need not share a block size, table size, AppendMagic or state.  Writes
+ * of 16 .. 49,152 bytes on handles with version 0, a table of at most 4,096 entries and a block of at
+ * most 2^26 that end at or before stream position 2^32 share one launch, a block of threads per
+ * handle; every other Write runs as ez_writer_write does, after that launch, inside the call.  Thread
+ * safety is the handles': no handle of the call may be in use by another thread. */
+int ez_writer_write_many(ez_writer *const *w, size_t count, const uint8_t *p, const uint64_t *ends,
+                         uint8_t *out, size_t cap, uint64_t *out_ends, int32_t *status);
+/* Introspection (tests, measurement): of the last ez_writer_write_many call of this process, how many
+ * Writes ran in the shared launch (counts[0]) and how many on their handle's own path (counts[1]). */
+int ez_writer_write_many_last(uint64_t counts[2]);
 int ez_writer_header(ez_writer *w, uint8_t *out, size_t cap, size_t *out_n); /* WriteHeader writer.go:342 */
 int ez_writer_break(ez_writer *w, uint8_t *out, size_t cap, size_t *out_n);  /* WriteBreak  writer.go:358 */
 int ez_writer_reset(ez_writer *w);                                          /* Reset       writer.go:149 (reset :187) */
@@ -335,7 +354,9 @@ int ez_decompress_kernel_last(void);
  * its route too: "hl:lds" / "hl:global" (K1L on the handle's ring, the Write staged in LDS / read from
  * global memory), "hl:batch zero-copy" / "hl:batch staged" (several such Writes in one call), "hw:pl" /
  * "hw:view" / "hw:multi" (the general kernel on the ring: one Write staged in LDS, one in the global
- * view, several Writes in one launch), "+gtab" appended when the table has more than 4096 entries. */
+ * view, several Writes in one launch), "+gtab" appended when the table has more than 4096 entries.
+ * ez_writer_write_many stores "hm:lds" (every Write shared its launch), "hm:lds+own" (some ran on
+ * their handle's own path) or "hm:own" (none shared the launch). */
 int ez_compress_route_last(char *buf, int cap);
 /* Testing: K1c (the chunk-parallel parse of long fresh streams, which proves each stream's parse
  * is Go's or gives it to K1L) counts its verdicts while counting is on: counts (6 words, may be
