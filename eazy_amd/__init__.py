@@ -559,6 +559,21 @@ class Reader:
         return bool(_lib().ez_reader_whole_decoded(self._h))
 
     @property
+    def whole_slot(self) -> int:
+        """Bytes of the slot the last whole-stream attempt decoded into, 0 if none (ez_reader_whole_slot)."""
+        L = _lib()
+        L.ez_reader_whole_slot.restype = C.c_uint64
+        L.ez_reader_whole_slot.argtypes = [C.c_void_p]
+        return int(L.ez_reader_whole_slot(self._h))
+
+    @property
+    def whole_launches(self) -> int:
+        """Decode launches the last whole-stream attempt made (ez_reader_whole_launches)."""
+        L = _lib()
+        L.ez_reader_whole_launches.argtypes = [C.c_void_p]
+        return int(L.ez_reader_whole_launches(self._h))
+
+    @property
     def ahead_count(self) -> int:
         """Read-aheads this NewReader(io.Reader) handle has made (ez_reader_ahead_count)."""
         L = _lib()
@@ -788,6 +803,39 @@ def decompress_batch_multi(comp, comp_off, out_off, block_size_limit: int = 0, d
     return out[: int(ooff[-1])], sizes[:count].astype(np.int64), status[:count]
 
 
+def decompressed_sizes_multi(comp, comp_off, block_size_limit: int = 0, devices=None):
+    """Host-memory decoded-size query over several devices (ez_decompressed_size_batch_multi): what
+    decompress_batch_multi would report for every stream given slots that are large enough, without
+    decoding.  Returns (sizes int64[count], statuses int32[count])."""
+    import numpy as np
+
+    c = _host_u8(comp)
+    coff = np.ascontiguousarray(comp_off, dtype=np.uint64)
+    count = len(coff) - 1
+    sizes = np.zeros(max(count, 1), np.uint64)
+    status = np.zeros(max(count, 1), np.int32)
+    devs = None if devices is None else (C.c_int * len(devices))(*devices)
+    L = _lib()
+    L.ez_decompressed_size_batch_multi.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.ez_decompressed_size_batch_multi(block_size_limit, c.ctypes.data, coff.ctypes.data, count, devs,
+                                              len(devices) if devices else 0, sizes.ctypes.data, status.ctypes.data))
+    return sizes[:count].astype(np.int64), status[:count]
+
+
+def decompress_batch_multi_sized(comp, comp_off, block_size_limit: int = 0, devices=None):
+    """Host-memory decode over several devices of a batch whose decoded lengths the caller does not
+    know -> (out bytes, out_off, sizes, statuses): decompressed_sizes_multi, a host prefix sum with
+    each size rounded up to 16 bytes, then decompress_batch_multi.  sizes and statuses are the
+    decode's."""
+    import numpy as np
+
+    need, _ = decompressed_sizes_multi(comp, comp_off, block_size_limit, devices)
+    out_off = np.zeros(len(need) + 1, np.uint64)
+    np.cumsum((need.astype(np.uint64) + np.uint64(15)) & ~np.uint64(15), out=out_off[1:])
+    out, sizes, status = decompress_batch_multi(comp, comp_off, out_off, block_size_limit, devices)
+    return out, out_off.astype(np.int64), sizes, status
+
+
 def compress_batch_writes(data, in_off, write_idx, write_end, block: int = MiB, htable: int = 1024,
                           append_magic: bool = True, stream=None, max_len: int | None = None,
                           max_writes: int | None = None, out: CompressedBatch | None = None) -> CompressedBatch:
@@ -886,15 +934,33 @@ def decompressed_size_chunk_last() -> int:
     return _lib().ez_decompressed_size_chunk_last()
 
 
+def select_size_route(kind: str = "") -> None:
+    """Force the fast route of later decompressed_sizes calls ('p' the parts route at any stream
+    length, given in_bytes; 'v' never the parts route; '' = automatic).  Tests and A/B only."""
+    _check(_lib().ez_select_size_route(ord(kind) if kind else 0))
+
+
+def decompressed_size_parts_last() -> tuple[int, int, int]:
+    """Of the last decompressed_sizes call, after its stream was synchronised: parts walked by the
+    parts route's first pass, parts taken as recorded, parts walked again (zeros: it did not run)."""
+    c = (C.c_uint64 * 3)()
+    L = _lib()
+    L.ez_decompressed_size_parts_last.argtypes = [C.POINTER(C.c_uint64)]
+    _check(L.ez_decompressed_size_parts_last(c))
+    return int(c[0]), int(c[1]), int(c[2])
+
+
 def decompressed_sizes(comp, comp_off, block_size_limit: int = 0, sizes=None, status=None, workspace=None,
-                       exact_only: bool = False, stream=None, max_len: int = 0):
+                       exact_only: bool = False, stream=None, max_len: int = 0, in_bytes: int = 0):
     """K2z: what decompress_batch would report for every stream comp[comp_off[s]:comp_off[s+1]]
     given a slot that is large enough, without decoding -> (sizes, status): the decoded length
     (for a stream that ends in an error, the bytes produced before it) and EZ_OK or that first
     error.  No output buffer is needed or touched; sizes are 64-bit (an output over 4 GiB is
     reported, not clamped).  max_len is an optional host hint, the longest INPUT stream in bytes:
-    it picks the fast kernel's chunk size and nothing else.  exact_only runs the exact decoder
-    alone.  Asynchronous on the stream."""
+    it picks the fast kernel's chunk size and nothing else.  in_bytes is an optional host hint,
+    comp_off[-1] - comp_off[0]: with it the parts route (every stream's chain cut over many waves)
+    can run; a wrong value costs speed, never results.  exact_only runs the exact decoder alone.
+    Asynchronous on the stream."""
     import torch
 
     _need_cuda(comp, comp_off)
@@ -906,7 +972,7 @@ def decompressed_sizes(comp, comp_off, block_size_limit: int = 0, sizes=None, st
         status = torch.empty(count, dtype=torch.int32, device=dev)
     if workspace is None and not exact_only:
         workspace = torch.empty(_lib().ez_decompress_workspace(count), dtype=torch.uint8, device=dev)
-    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, None, sizes.data_ptr(), status.data_ptr(), count, max_len)
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, None, sizes.data_ptr(), status.data_ptr(), count, max_len, in_bytes, 0)
     ws = None if exact_only else workspace.data_ptr()
     _check(_lib().ez_decompressed_size_batch(block_size_limit, C.byref(b), ws, _stream_ptr(stream)))
     return sizes, status

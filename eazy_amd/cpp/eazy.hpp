@@ -823,4 +823,26 @@ inline Err DecompressBatchMulti(const std::vector<std::vector<uint8_t>> &streams
     return Err::OK;
 }
 
+
+// ez_decompressed_size_batch_multi: every stream's decoded length and first error (or OK) without
+// decoding, over the devices' shards: out[k] = (the bytes stream k decodes to, for a stream that ends
+// in an error the bytes before it; its status).  A caller sizes DecompressBatchMulti's slots from it.
+inline Err DecompressedSizeBatchMulti(const std::vector<std::vector<uint8_t>> &streams, std::vector<std::pair<uint64_t, Err>> &out,
+                                      const std::vector<int> &devices = {}, int64_t block_size_limit = 0) {
+    std::vector<uint64_t> off(streams.size() + 1, 0);
+    for (size_t k = 0; k < streams.size(); k++) off[k + 1] = off[k] + streams[k].size();
+    std::vector<uint8_t> in;
+    in.reserve(off.back() + 1);
+    for (const auto &b : streams) in.insert(in.end(), b.begin(), b.end());
+    std::vector<uint64_t> sizes(streams.size() + 1, 0);
+    std::vector<int32_t> status(streams.size() + 1, 0);
+    const int st = ez_decompressed_size_batch_multi(block_size_limit, in.data(), off.data(), streams.size(),
+                                                    devices.empty() ? nullptr : devices.data(), (int)devices.size(), sizes.data(), status.data());
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: DecompressedSizeBatchMulti: invalid arguments");
+    if (st != EZ_OK) return (Err)st;
+    out.assign(streams.size(), {});
+    for (size_t k = 0; k < streams.size(); k++) out[k] = {sizes[k], (Err)status[k]};
+    return Err::OK;
+}
+
 }  // namespace eazy

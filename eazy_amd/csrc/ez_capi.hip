@@ -297,6 +297,7 @@ extern "C" int ez_decompressed_size_batch(int64_t block_size_limit, const ez_bat
     a.count = b->count;
     a.block_size_limit = block_size_limit;
     a.slow = (uint32_t *)workspace;
+    a.in_bytes = b->in_bytes;  // the batch's input extent, if the caller knows it: the parts route needs it
     EZ_HIP(ez::launch_decompress_size(a, b->max_len, (hipStream_t)hip_stream));
     return EZ_OK;
 }
@@ -304,6 +305,20 @@ extern "C" int ez_decompressed_size_batch(int64_t block_size_limit, const ez_bat
 extern "C" int ez_decompressed_size_chunk(uint64_t max_len) { return ez::size_chunk(max_len); }
 
 extern "C" int ez_decompressed_size_chunk_last(void) { return ez::last_size_chunk(); }
+
+extern "C" int ez_select_size_route(int kind) {
+    if (kind != 0 && kind != 'p' && kind != 'v') return EZ_EINVAL;
+    ez::select_size_route(kind);
+    return EZ_OK;
+}
+
+extern "C" int ez_decompressed_size_parts_last(uint64_t counts[3]) {
+    if (!counts) return EZ_EINVAL;
+    counts[0] = counts[1] = counts[2] = 0;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    EZ_HIP(ez::size_parts_last(counts));
+    return EZ_OK;
+}
 
 // Frees the device scratch the batch calls keep between calls (no reference counterpart; like a
 // caching allocator's empty_cache): the K1 / K1c scratch and K2j workspaces per (device, HIP stream),
@@ -318,6 +333,7 @@ extern "C" int ez_release_cached(int device) {
         if (hipSetDevice(d) != hipSuccess) return EZ_EDEVICE;
         k1_cache().trim(d);
         ez::jump_cache().trim(d);
+        ez::size_cache().trim(d);
         reader_release_cached(d);
         writer_release_cached(d);
     }

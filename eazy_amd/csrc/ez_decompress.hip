@@ -12,6 +12,7 @@
 // out[pos+k] = out[pos - D + (k mod D)], always reading bytes written by
 // earlier tokens, so every token is one hazard-free parallel pass.
 #include "ez_format.h"
+#include "ez_cache.h"
 #include "ez_internal.h"
 #include "ez_wave.h"
 #include "ez_bytes.h"
@@ -320,16 +321,35 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
     a.dry = 1;
     a.out = nullptr;
     a.out_off = nullptr;
-    const int chunk = a.slow ? size_route(max_len, a.count) : 0;
-    g_last_size_chunk = chunk;
-    if (a.count == 0) return hipSuccess;
-    if (!a.slow) {
+    int chunk = a.slow ? size_route(max_len, a.count) : 0;
+    // The parts route (ez_decompress_parts.hip) needs the batch's extent to size its records without
+    // a read-back: only with the caller's in_bytes hint, and where it measured faster than a wave per
+    // stream (size_parts_chunk) or is forced.  Without its scratch the batch takes the wave route.
+    const int sel = selected_size_route();
+    const int pchunk = a.slow && a.count != 0 && a.in_bytes != 0 && a.count <= (1u << 20) && sel != 'v'
+                           ? size_parts_chunk(max_len, a.count, a.in_bytes, sel == 'p')
+                           : 0;
+    if (a.count == 0 || !a.slow) {
+        g_last_size_chunk = chunk;
+        size_parts_none();
+        if (a.count == 0) return hipSuccess;
         const uint64_t grid = a.count < (1u << 30) ? a.count : (1u << 30);
         hipLaunchKernelGGL(k2_decompress, dim3((unsigned)grid), dim3(64), 0, st, a);
         return hipGetLastError();
     }
     hipError_t e = hipMemsetAsync(a.slow, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
+    CacheLease lease;  // (the parts route's scratch, until the wave route behind it is launched)
+    if (pchunk) {
+        e = launch_size_parts(a, pchunk, sel != 'p', st, lease, &a.size_gate, &a.size_base);
+        if (e == hipSuccess) chunk = pchunk;
+        else if (e != hipErrorOutOfMemory) return e;
+        else a.size_gate = nullptr;
+    }
+    if (!a.size_gate) size_parts_none();
+    a.jws = nullptr;  // (the parts route's scratch, if the caller gave one: not the exact decoder's business)
+    a.jws_cap = 0;
+    g_last_size_chunk = chunk;
     if ((e = launch_size_fast(a, chunk, st)) != hipSuccess) return e;
     const uint64_t exact_grid = a.count < 4096 ? a.count : 4096;
     hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);

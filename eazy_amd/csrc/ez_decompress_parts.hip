@@ -1,0 +1,328 @@
+// ez_decompress_parts.hip — K2z's parts route: every stream's token chain cut over many waves, for
+// the few long streams that the wave route (ez_decompress_size.hip) gives one wave each.
+//
+// The steps are ez_k2_parts.h's.  Three kernels on the caller's stream:
+//   kp_init   checks the caller's in_bytes hint against the real extent and lays the streams' parts
+//             out (an exclusive scan of every stream's part count; on the automatic route a stream
+//             that starts with tokens over half of it gets none, kp_probe_wave); on a mismatch it
+//             leaves the gate closed: the next two kernels do nothing.  The wave route, launched
+//             behind them with the gate and the layout as arguments, sizes every stream if the
+//             gate is closed, else the streams without parts;
+//   kp_first  a wave per part, grid-stride: stage the part and the warm-up chunk before it in LDS,
+//             speculate, verify and repair, sum, reduce, and write the part's record;
+//   kp_order  a wave per stream: follows the true chain through the records, 64 of them per load,
+//             walks again the parts whose record starts elsewhere, and ends as the wave route does:
+//             out_size[s] and EZ_OK, or the stream on the slow list for the exact decoder run dry.
+// The scratch ([header][part bases: count + 1][records]) is sized from the hint alone, so the call
+// never waits for the stream; it is leased from a cache per (device, HIP stream).
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "ez_bytes.h"
+#include "ez_cache.h"
+#include "ez_internal.h"
+#include "ez_k2_parts.h"
+#include "ez_wave.h"
+
+namespace ez {
+namespace {
+
+// the scratch's header words
+enum : int { kHGate = 0, kHParts = 1, kHLaunched = 2, kHJoined = 3, kHWalked = 4, kHWords = 16 };
+constexpr int kInitThreads = 1024;
+
+template <int C>
+__global__ __launch_bounds__(kInitThreads) void kp_init(DecompressArgs A, uint32_t *hdr, uint32_t *base, uint64_t cap, int probe) {
+    __shared__ uint64_t sums[kInitThreads];
+    const int t = (int)threadIdx.x;
+    const uint64_t per = (A.count + kInitThreads - 1) / kInitThreads;
+    const uint64_t lo = (uint64_t)t * per < A.count ? (uint64_t)t * per : A.count;
+    const uint64_t hi = lo + per < A.count ? lo + per : A.count;
+    uint64_t n = 0;
+    for (uint64_t s = lo; s < hi; s++) {
+        const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
+        uint32_t parts = kp_parts_of(nb64, C);
+        if (probe && parts) {
+            const uint8_t *b = A.in + A.in_off[s];
+            const uint32_t nb = (uint32_t)nb64;
+            if (kp_probe_wave([=](uint32_t p) { return p + 16 <= nb ? ld16v(b + p) : ld_clamped(b + p, b, b + nb); }, nb)) parts = 0;
+        }
+        base[s] = parts;
+        n += parts;
+    }
+    sums[t] = n;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t run = 0;
+        for (int k = 0; k < kInitThreads; k++) {
+            const uint64_t v = sums[k];
+            sums[k] = run;
+            run += v;
+        }
+        // the records are sized from the hint: nothing indexes them unless the real extent is within it
+        const bool ok = A.in_off[A.count] >= A.in_off[0] && A.in_off[A.count] - A.in_off[0] <= A.in_bytes && run <= cap;
+        hdr[kHParts] = ok ? (uint32_t)run : 0u;
+        hdr[kHGate] = ok ? 1u : 0u;
+        base[A.count] = ok ? (uint32_t)run : 0u;
+    }
+    __syncthreads();
+    uint64_t run = sums[t];
+    for (uint64_t s = lo; s < hi; s++) {  // the part counts become their exclusive scan, in place
+        const uint32_t parts = base[s];
+        base[s] = (uint32_t)run;  // (wraps only where the gate stays closed)
+        run += parts;
+    }
+}
+
+// One part of the stream b[0 .. nb) at ps, by the whole wave: its record for the chain that enters at
+// the speculative position (known false: the first pass) or at the true one e (the in-order pass).
+template <int C>
+__device__ KpRec part_walk(uint8_t *stage, uint32_t (*bm)[C / 32 + 1], const uint8_t *b, uint32_t nb, uint32_t ps, bool known, uint32_t e,
+                           int32_t lim32, int64_t limit) {
+    const int lane = lane_id();
+    __syncthreads();  // (the previous part's reads are done)
+    const uint32_t sbase = kp_stage_base(ps, C);
+    const uint32_t pe = nb - ps > kp_part_bytes(C) ? ps + kp_part_bytes(C) : nb;
+    const uint32_t need = pe + 16 - sbase;  // (at most kp_stage_bytes(C), a multiple of 16)
+    for (uint32_t o = (uint32_t)lane * 16; o < need; o += kWave * 16) {
+        const uint32_t y = sbase + o;
+        V16 v{0, 0};
+        if (y + 16 <= nb) v = ld16v(b + y);
+        else if (y < nb) v = ld_clamped(b + y, b, b + nb);
+        typedef uint64_t __attribute__((aligned(8))) u64a;
+        *(u64a *)(stage + o) = v.lo;
+        *(u64a *)(stage + o + 8) = v.hi;
+    }
+    __syncthreads();
+    const KzWin w{stage, sbase};
+    uint32_t first;
+    const uint32_t sexit = kp_spec<C>(w, ps, lane, nb, known, e, bm[lane], first);
+    uint32_t a = kp_entry(lane, ps, C, known, e, first, __shfl_up(sexit, 1, kWave));
+    uint32_t x = kz_verify<C>(w, ps, lane, nb, bm[lane], sexit, a);
+    bool settled = true;
+    for (int round = 0;; round++) {
+        const uint32_t px = __shfl_up(x, 1, kWave);
+        const uint64_t wrong = wballot(lane > 0 && a != px);
+        if (wrong == 0) break;
+        if (round >= kZFixRounds) {
+            settled = false;
+            break;
+        }
+        const int jf = ffs64(wrong);
+        kz_fix<C>(w, ps, lane, nb, bm[lane], sexit, jf, (uint32_t)__shfl((int)x, jf - 1, kWave), a, x);
+    }
+    KpRec rec{0, kPNoEntry, 0, 0, 0};
+    if (!settled) return rec;
+    const KzSum r = kz_sum<C>(w, ps, lane, nb, a, x, lim32, limit);
+    uint64_t io = r.out;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint64_t v = __shfl_up(io, d, kWave);
+        if (lane >= d) io += v;
+    }
+    uint32_t md = r.maxd;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) md = max(md, (uint32_t)__shfl_xor((int)md, d, kWave));
+    // (kp_append over the lanes in order)
+    const bool bad = wballot((r.fl & kZBad) != 0) != 0;
+    const uint64_t rm = wballot((r.fl & kZReset) != 0);
+    const bool late = wballot((r.fl & kZReset) && ((r.fl & kZResetLate) || io != r.out)) != 0;
+    rec.out = __shfl(io, kWave - 1, kWave);
+    rec.ent = (uint32_t)__shfl((int)a, 0, kWave);
+    rec.exit = (uint32_t)__shfl((int)x, kWave - 1, kWave);
+    rec.maxd = md;
+    rec.fl = bad ? kZBad : 0u;
+    if (rm) rec.fl |= kZReset | (late ? kZResetLate : 0u) | ((uint32_t)__shfl((int)r.fl, 63 - __builtin_clzll(rm), kWave) & 0xff00u);
+    return rec;
+}
+
+template <int C>
+__global__ __launch_bounds__(64) void kp_first(DecompressArgs A, uint32_t *hdr, const uint32_t *base, KpRec *recs) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kp_stage_bytes(C)];
+    __shared__ uint32_t bm[kZLanes][C / 32 + 1];
+    if (hdr[kHGate] == 0) return;
+    const uint32_t parts = hdr[kHParts];
+    const int64_t limit = A.block_size_limit;
+    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    uint32_t done = 0;
+    for (uint32_t g = blockIdx.x; g < parts; g += gridDim.x) {
+        const uint64_t s = kp_stream_of(base, A.count, g);
+        const uint32_t nb = (uint32_t)(A.in_off[s + 1] - A.in_off[s]);  // (below 2^31: the stream has parts)
+        const uint32_t ps = (g - base[s]) * kp_part_bytes(C);
+        const KpRec r = part_walk<C>(stage, bm, A.in + A.in_off[s], nb, ps, false, 0, lim32, limit);
+        if (lane_id() == 0) recs[g] = r;
+        done++;
+    }
+    if (lane_id() == 0 && done) atomicAdd(&hdr[kHLaunched], done);
+}
+
+template <int C>
+__global__ __launch_bounds__(64) void kp_order(DecompressArgs A, uint32_t *hdr, const uint32_t *base, const KpRec *recs) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kp_stage_bytes(C)];
+    __shared__ uint32_t bm[kZLanes][C / 32 + 1];
+    if (hdr[kHGate] == 0) return;
+    const int lane = lane_id();
+    const int64_t limit = A.block_size_limit;
+    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    uint32_t joined = 0, walked = 0;
+    for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
+        const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
+        const uint8_t *b = A.in + A.in_off[s];
+        KpState S = kp_start(nb64);
+        const uint32_t nb = S.bad ? 0u : (uint32_t)nb64;
+        const uint32_t n = base[s + 1] - base[s];
+        if (n == 0) continue;  // (the wave route's, launched behind this kernel)
+        const KpRec *rs = recs + base[s];
+        uint32_t j = 0;
+        while (!S.bad && j < n) {
+            KpRec mine{0, kPNoEntry, 0, 0, 0};
+            if (j + (uint32_t)lane < n) mine = rs[j + lane];
+            const uint32_t m = n - j < (uint32_t)kWave ? n - j : (uint32_t)kWave;
+            for (uint32_t k = 0; k < m && !S.bad; k++) {
+                const uint32_t ps = (j + k) * kp_part_bytes(C);
+                const uint32_t pe = nb - ps > kp_part_bytes(C) ? ps + kp_part_bytes(C) : nb;
+                KpRec r;
+                r.out = __shfl(mine.out, (int)k, kWave);
+                r.ent = (uint32_t)__shfl((int)mine.ent, (int)k, kWave);
+                r.exit = (uint32_t)__shfl((int)mine.exit, (int)k, kWave);
+                r.maxd = (uint32_t)__shfl((int)mine.maxd, (int)k, kWave);
+                r.fl = (uint32_t)__shfl((int)mine.fl, (int)k, kWave);
+                const int cls = kp_class(S, pe, r);
+                if (cls == kPPass) continue;
+                if (cls == kPWalk) {
+                    r = part_walk<C>(stage, bm, b, nb, ps, true, S.e, lim32, limit);
+                    walked++;
+                } else {
+                    joined++;
+                }
+                kp_take(S, r);
+            }
+            // the next part the chain can enter: the parts a token spans are not even loaded
+            j += m;
+            const uint32_t at = S.e / kp_part_bytes(C);
+            j = at > j ? at : j;
+        }
+        const bool ok = kp_end_ok(S, nb);
+        if (lane == 0) {
+            if (!ok) {
+                const uint32_t at = atomicAdd(&A.slow[0], 1u);
+                A.slow[1 + at] = (uint32_t)s;
+            } else {
+                A.out_size[s] = S.total;
+                if (A.status) A.status[s] = EZ_OK;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (joined) atomicAdd(&hdr[kHJoined], joined);
+        if (walked) atomicAdd(&hdr[kHWalked], walked);
+    }
+}
+
+template <int C>
+hipError_t launch_parts(const DecompressArgs &a, uint8_t *w, uint64_t cap, int probe, hipStream_t st) {
+    uint32_t *hdr = (uint32_t *)w;
+    uint32_t *base = hdr + kHWords;
+    KpRec *recs = (KpRec *)(w + (((size_t)kHWords + a.count + 1) * 4 + 15) / 16 * 16);
+    hipError_t e = hipMemsetAsync(hdr, 0, kHWords * 4, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kp_init<C>, dim3(1), dim3(kInitThreads), 0, st, a, hdr, base, cap, probe);
+    // the chip's LDS holds two such blocks per CU; the parts beyond go round the grid
+    hipLaunchKernelGGL(kp_first<C>, dim3((unsigned)(cap < 2048 ? cap : 2048)), dim3(64), 0, st, a, hdr, base, recs);
+    hipLaunchKernelGGL(kp_order<C>, dim3((unsigned)(a.count < 2048 ? a.count : 2048)), dim3(64), 0, st, a, hdr, base, recs);
+    return hipGetLastError();
+}
+
+struct PartsLast {
+    std::mutex mu;
+    bool ran = false;
+    int dev = 0;
+    void *stream = nullptr;
+} g_last;
+
+}  // namespace
+
+DevCache &size_cache() {
+    static DevCache *c = new DevCache();  // (never destroyed: no hipFree after the runtime's teardown)
+    return *c;
+}
+
+static std::atomic<int> g_size_route{0};  // 0: automatic; 'p', 'v'
+void select_size_route(int v) { g_size_route = v; }
+int selected_size_route() { return g_size_route; }
+
+void size_parts_none() {
+    std::lock_guard<std::mutex> g(g_last.mu);
+    g_last.ran = false;
+}
+
+// bytes of scratch the route needs for a batch (either chunk size): a synchronous caller that owns
+// its scratch (a Reader handle) sizes it with this and passes it as DecompressArgs.jws / jws_cap
+uint64_t size_parts_workspace_bytes(uint64_t count, uint64_t in_bytes) {
+    const uint64_t cap = in_bytes / kp_part_bytes(256) + count + 1;
+    return (((uint64_t)kHWords + count + 1) * 4 + 15) / 16 * 16 + cap * sizeof(KpRec);
+}
+
+hipError_t launch_size_parts(const DecompressArgs &a, int chunk, bool probe, hipStream_t st, CacheLease &lease, const uint32_t **gate,
+                             const uint32_t **base) {
+    const uint32_t P = kp_part_bytes((uint32_t)chunk);
+    const uint64_t cap = a.in_bytes / P + a.count + 1;  // every stream's parts: at most its bytes / P, rounded up
+    if (cap >= (1ull << 31)) return hipErrorOutOfMemory;
+    const size_t bytes = (((size_t)kHWords + a.count + 1) * 4 + 15) / 16 * 16 + (size_t)cap * sizeof(KpRec);
+    uint8_t *w = (uint8_t *)a.jws;
+    if (w) {  // the caller's own scratch: no counters to report afterwards
+        if (a.jws_cap < bytes) return hipErrorOutOfMemory;
+        size_parts_none();
+    } else {
+        int dev = 0;
+        const hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        lease = size_cache().acquire(dev, (void *)st);
+        if (!lease->ensure(bytes)) return hipErrorOutOfMemory;  // (the caller takes the wave route)
+        w = (uint8_t *)lease->p;
+        std::lock_guard<std::mutex> g(g_last.mu);
+        g_last.ran = true;
+        g_last.dev = dev;
+        g_last.stream = (void *)st;
+    }
+    *gate = (const uint32_t *)w + kHGate;
+    *base = (const uint32_t *)w + kHWords;
+    return chunk == 1024 ? launch_parts<1024>(a, w, cap, probe, st) : launch_parts<256>(a, w, cap, probe, st);
+}
+
+// of the last query: parts launched, parts whose record the true chain took, parts walked again
+// (zeros where the parts route did not run); the caller has synchronised the query's stream
+hipError_t size_parts_last(uint64_t counts[3]) {
+    counts[0] = counts[1] = counts[2] = 0;
+    bool ran;
+    int dev;
+    void *stream;
+    {
+        std::lock_guard<std::mutex> g(g_last.mu);
+        ran = g_last.ran;
+        dev = g_last.dev;
+        stream = g_last.stream;
+    }
+    if (!ran) return hipSuccess;
+    int cur = 0;
+    hipError_t e = hipGetDevice(&cur);
+    if (e != hipSuccess) return e;
+    if (cur != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
+    {
+        CacheLease lease = size_cache().acquire(dev, stream);
+        if (lease->p && lease->cap >= kHWords * 4) {  // (else released since: nothing to report)
+            uint32_t h[kHWords];
+            e = hipMemcpy(h, lease->p, sizeof h, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) {
+                counts[0] = h[kHLaunched];
+                counts[1] = h[kHJoined];
+                counts[2] = h[kHWalked];
+            }
+        }
+    }
+    if (cur != dev) (void)hipSetDevice(cur);
+    return e;
+}
+
+}  // namespace ez

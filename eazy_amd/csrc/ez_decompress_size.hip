@@ -35,10 +35,12 @@ __global__ __launch_bounds__(64) void k2z_size(DecompressArgs A) {
     constexpr int W = C / 32;
     __shared__ __attribute__((aligned(16))) uint8_t stage[kz_stage_bytes(C)];
     __shared__ uint32_t bm[kZLanes][W + 1];  // (+1: the lanes' rows on distinct banks)
+    const bool parted = A.size_gate && *A.size_gate;  // (the parts route sized the streams that have parts)
     const int lane = lane_id();
     const int64_t limit = A.block_size_limit;
     const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
     for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
+        if (parted && A.size_base[s] != A.size_base[s + 1]) continue;
         const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
         const uint8_t *b = A.in + A.in_off[s];
         bool bad = nb64 >= (1ull << 31);
@@ -113,9 +115,11 @@ __global__ __launch_bounds__(64) void k2z_size(DecompressArgs A) {
 // chip's lanes that beats a wave per stream, whose lanes mostly repeat each other's walks on a stream
 // of a few dozen chunks (C1: DESIGN §4 K2z).
 __global__ __launch_bounds__(64) void k2z_lane(DecompressArgs A) {
+    const bool parted = A.size_gate && *A.size_gate;  // (the parts route sized the streams that have parts)
     const int64_t limit = A.block_size_limit;
     const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
     for (uint64_t s = (uint64_t)blockIdx.x * kWave + threadIdx.x; s < A.count; s += (uint64_t)gridDim.x * kWave) {
+        if (parted && A.size_base[s] != A.size_base[s + 1]) continue;
         const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
         const uint8_t *b = A.in + A.in_off[s];
         uint64_t total = 0;
@@ -150,6 +154,24 @@ int size_chunk(uint64_t max_len) { return max_len == 0 ? 256 : (max_len <= 4096 
 constexpr uint64_t kZLaneStreams = 4096;
 int size_route(uint64_t max_len, uint64_t count) {
     return max_len != 0 && max_len <= 4096 && count >= kZLaneStreams ? 1 : size_chunk(max_len);
+}
+
+// The parts route's chunk for a batch whose caller gave its input bytes, 0: the wave route.  Forced
+// (ez_select_size_route('p')): at any length, 1,024 where the wave route takes 1,024, else 256.
+// Automatic, only where it measured faster than a wave per stream (tools/size_parts_bench.py, DESIGN
+// §4 K2z; ms, wave / parts 256 / parts 1,024):
+//   one stream from 240 KiB of input on, chunk 1,024 (one log stream of 0.25 MB compressed 1.76 / 0.70 /
+//     0.38, 0.5 MB 3.51 / 0.99 / 0.39, 2 MB 9.61 / 3.19 / 0.40, 8 MB 38.7 / 15.4 / 0.77, 32 MB 157 / 62.6 /
+//     1.81: chunk 256 leaves a quarter of the parts to the one wave that walks them again);
+//   2 to 64 streams whose longest is over 512 KiB, chunk 256 (C4s, 64 x 0.9 MB: 7.23 / 1.37 / 2.21; C4's
+//     literals are the wave route's by the probe: 0.073 on the wave route alone, 0.052 automatic).
+// More streams keep a wave each, which fills the chip (1,024 x 1 MiB logs 4.06 / 4.48 / 6.64, C2 2.25 /
+// 3.58 / 6.25).
+int size_parts_chunk(uint64_t max_len, uint64_t count, uint64_t in_bytes, bool forced) {
+    if (forced) return size_chunk(max_len) == 1024 ? 1024 : 256;
+    (void)in_bytes;
+    if (count == 1) return max_len >= (240u << 10) ? 1024 : 0;
+    return count <= 64 && max_len > (512u << 10) ? 256 : 0;
 }
 
 hipError_t launch_size_fast(const DecompressArgs &a, int chunk, hipStream_t st) {

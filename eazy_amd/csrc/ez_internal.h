@@ -125,7 +125,8 @@ struct DecompressArgs {
     uint64_t breaks_cap;
     int64_t *end_state;
     // K2j's workspace, optional (jump_workspace_bytes): a synchronous caller (a Reader handle) passes
-    // one it owns; without it the launcher keeps one per (device, HIP stream)
+    // one it owns; without it the launcher keeps one per (device, HIP stream).  The size query takes
+    // the parts route's scratch the same way (size_parts_workspace_bytes)
     void *jws;
     uint64_t jws_cap;
     int force;                // batch: the first K2 kernel ('r', 't', ...; 0 = the automatic / selected one)
@@ -146,6 +147,11 @@ struct DecompressArgs {
     // batch, the size query (K2z, ez_decompressed_size_batch): the exact decoder reads every stream to
     // EOF with an unbounded capacity and stores nothing; out and out_off are not touched (may be null)
     int dry;
+    // K2z's wave and lane kernels behind the parts route (ez_decompress_parts.hip), optional: they size
+    // the whole batch where the device word size_gate is 0 (the parts route found the in_bytes hint too
+    // small), else only the streams s without parts (size_base[s] == size_base[s + 1])
+    const uint32_t *size_gate;
+    const uint32_t *size_base;
 };
 
 // words of workspace the two-level batch decoder needs
@@ -229,6 +235,20 @@ int size_chunk(uint64_t max_len);  // the wave kernel's chunk bytes for a hint
 int size_route(uint64_t max_len, uint64_t count);  // 1: the lane-per-stream kernel; else the wave kernel's chunk
 int last_size_chunk();             // the route of the last query (0: the exact decoder alone; -1: none yet)
 hipError_t launch_size_fast(const DecompressArgs &a, int route, hipStream_t s);
+// K2z's parts route (ez_decompress_parts.hip): every stream's chain cut over many waves, chunk 256 or
+// 1,024; needs a.in_bytes.  probe: streams that start with tokens over half of them get no parts.
+// *gate, *base: DecompressArgs.size_gate and size_base for the wave route launched behind it; lease: the scratch, held until that launch.  (hipErrorOutOfMemory: the scratch
+// could not be had, nothing was launched)
+int size_parts_chunk(uint64_t max_len, uint64_t count, uint64_t in_bytes, bool forced);  // its chunk; 0: the wave route
+class CacheLease;
+hipError_t launch_size_parts(const DecompressArgs &a, int chunk, bool probe, hipStream_t s, CacheLease &lease, const uint32_t **gate,
+                             const uint32_t **base);
+uint64_t size_parts_workspace_bytes(uint64_t count, uint64_t in_bytes);  // its scratch where the caller owns it (a.jws / a.jws_cap)
+DevCache &size_cache();            // its scratch per (device, HIP stream) otherwise
+void select_size_route(int v);     // 0 = automatic, 'p' parts at any length, 'v' the wave route (tests, A/B)
+int selected_size_route();
+void size_parts_none();            // the last query did not take the parts route
+hipError_t size_parts_last(uint64_t counts[3]);  // parts launched, taken as recorded, walked again
 bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once, ez_k1_probe.hip)
 bool lds_mskor_in_lane_order();     // the LDS property k1_lean's one-atomic visit relies on (checked once)
 hipError_t launch_pack(const uint8_t *slots, const uint64_t *slot_off, const uint64_t *sizes, uint64_t count,

@@ -1,5 +1,5 @@
 // ez_multi.hip — host batches over several devices (ez_compress_batch_multi,
-// ez_decompress_batch_multi): contiguous shards of whole streams, one host thread and one pooled HIP
+// ez_decompress_batch_multi, ez_decompressed_size_batch_multi): contiguous shards of whole streams, one host thread and one pooled HIP
 // stream per shard, each running the single-device batch calls of ez_capi.hip.
 #include <hip/hip_runtime.h>
 
@@ -309,6 +309,42 @@ extern "C" int ez_decompress_batch_multi(int64_t block_size_limit, const uint8_t
             const int r = ez_decompress_batch(block_size_limit, &b, x.r->ws.p, x.r->st);
             if (r != EZ_OK) return r;
             if (no) EZ_HIP(hipMemcpyAsync(out + ob, x.r->out.p, no, hipMemcpyDeviceToHost, x.r->st));
+            EZ_HIP(hipMemcpyAsync(out_size + x.first, x.r->size.p, 8 * c, hipMemcpyDeviceToHost, x.r->st));
+            if (status) EZ_HIP(hipMemcpyAsync(status + x.first, x.r->status.p, 4 * c, hipMemcpyDeviceToHost, x.r->st));
+            EZ_HIP(hipStreamSynchronize(x.r->st));
+            return EZ_OK;
+        });
+    } catch (...) {
+        return EZ_EDEVICE;
+    }
+}
+
+// The decoded sizes of a host batch (K2z per shard): the shards, pooled resources and per-shard threads
+// of ez_decompress_batch_multi, without an output.
+extern "C" int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in, const uint64_t *in_off, uint64_t count,
+                                                const int *devices, int ndev, uint64_t *out_size, int32_t *status) {
+    if (!in_off || !out_size) return EZ_EINVAL;
+    std::vector<int> devs;
+    int e = resolve_devices(devices, ndev, devs);
+    if (e != EZ_OK) return e;
+    if (count == 0) return EZ_OK;
+    DeviceGuard keep(-1);
+    try {
+        Shards sh = make_shards(in_off, count, devs);
+        return each_shard(sh, [&](Shard &x) -> int {
+            const uint64_t c = x.count, ib = in_off[x.first];
+            const std::vector<uint64_t> ioff = rebased(in_off, x);
+            const uint64_t nb = ioff[c], mx = max_span(ioff);
+            if (x.r->in.ensure(nb + 64) || x.r->in_off.ensure(8 * (c + 1)) || x.r->size.ensure(8 * c) || x.r->status.ensure(4 * c) ||
+                x.r->ws.ensure(ez_decompress_workspace(c) + 64))
+                return EZ_EDEVICE;
+            if (nb) EZ_HIP(hipMemcpyAsync(x.r->in.p, in + ib, nb, hipMemcpyHostToDevice, x.r->st));
+            EZ_HIP(hipMemcpyAsync(x.r->in_off.p, ioff.data(), 8 * (c + 1), hipMemcpyHostToDevice, x.r->st));
+            // (the longest input stream and the shard's input bytes given: the query's route needs no read-back)
+            ez_batch b{x.r->in.as<uint8_t>(), x.r->in_off.as<uint64_t>(), nullptr, nullptr, x.r->size.as<uint64_t>(), x.r->status.as<int32_t>(),
+                       c, mx, nb, 0};
+            const int r = ez_decompressed_size_batch(block_size_limit, &b, x.r->ws.p, x.r->st);
+            if (r != EZ_OK) return r;
             EZ_HIP(hipMemcpyAsync(out_size + x.first, x.r->size.p, 8 * c, hipMemcpyDeviceToHost, x.r->st));
             if (status) EZ_HIP(hipMemcpyAsync(status + x.first, x.r->status.p, 4 * c, hipMemcpyDeviceToHost, x.r->st));
             EZ_HIP(hipStreamSynchronize(x.r->st));

@@ -29,7 +29,9 @@ struct ez_reader {
     int whole = 0;             // the caller's b is the whole stream (NewReaderBytes / ResetBytes)
     int tried = 0;             // tried since the last reset
     int ahead_on = 0;          // Reads are served from a_out[a_at .. a_n)
-    DBuf a_in, a_out, a_meta, a_ws, a_brk;  // kept across resets (grown, never shrunk)
+    uint64_t w_slot = 0;       // the slot the last whole-stream attempt decoded into (ez_reader_whole_slot)
+    int w_launches = 0;        // the decode launches it made (ez_reader_whole_launches)
+    DBuf a_in, a_out, a_meta, a_ws, a_brk, a_qws;  // kept across resets (grown, never shrunk); a_qws: the size query's scratch
     uint64_t a_n = 0, a_at = 0;             // bytes decoded; bytes served
     size_t a_blen = 0;                      // the input decoded (len(r.b) at the first Read)
     std::vector<uint64_t> brk;              // the Break metas' output positions, ascending
@@ -68,7 +70,7 @@ extern "C" int ez_reader_new(int device, ez_reader **out) {
 extern "C" void ez_reader_free(ez_reader *r) {
     if (!r) return;
     DeviceGuard g(r->device);
-    for (DBuf *b : {&r->in, &r->obuf[0], &r->obuf[1], &r->dstate, &r->meta, &r->a_in, &r->a_out, &r->a_meta, &r->a_ws, &r->a_brk,
+    for (DBuf *b : {&r->in, &r->obuf[0], &r->obuf[1], &r->dstate, &r->meta, &r->a_in, &r->a_out, &r->a_meta, &r->a_ws, &r->a_brk, &r->a_qws,
                     &r->s_meta, &r->s_ws})
         b->release();
     if (r->stage) (void)hipHostFree(r->stage);
@@ -106,6 +108,10 @@ extern "C" int ez_reader_set_whole(ez_reader *r, int whole) {
 }
 
 extern "C" int ez_reader_whole_decoded(const ez_reader *r) { return r->ahead_on; }
+
+extern "C" uint64_t ez_reader_whole_slot(const ez_reader *r) { return r->w_slot; }
+
+extern "C" int ez_reader_whole_launches(const ez_reader *r) { return r->w_launches; }
 
 extern "C" int64_t ez_reader_ahead_count(const ez_reader *r) { return r->s_count; }
 
@@ -223,11 +229,15 @@ int hand_history(ez_reader *r, DBuf &to, const uint8_t *end, size_t H2, bool dra
 }
 
 // Whole-stream decode (NewReaderBytes then Read to the end, the reference's common use): the batch
-// path decodes b as one stream -- K2t, every lane of a wave on its tokens -- into a device slot, and the
-// Reads are then served from that output.  The slot starts at 8 x b_len and grows 4x while K2t reports
-// it too small (up to 1 GiB).  The decoders record every Break meta's output position, so the Reads stop
-// at each with ErrBreak as Read by Read does (reader.go:312-313), and the Reader's state at the end
-// (len(r.block), r.pos), so that input a caller supplies after the stream (a Reader set after
+// path decodes b as one stream -- K2j, or K2t for a short one -- into a device slot, and the Reads are
+// then served from that output.  The slot is exact: after the upload the decoded-size query (K2z, the
+// parts route for a long stream) runs on the handle's stream, and its size and status come back with
+// the meta block.  A stream the query gives an error, or one that decodes to more than 1 GiB, is left
+// to Read-by-Read decoding at once, with no output buffer allocated; any other is decoded once.  (The
+// decode cannot find that slot too small; if it reports so all the same, the stream is left to Read by
+// Read as well: the slot does not grow.)  The decoders record every Break meta's output position, so
+// the Reads stop at each with ErrBreak as Read by Read does (reader.go:312-313), and the Reader's state
+// at the end (len(r.block), r.pos), so that input a caller supplies after the stream (a Reader set after
 // NewReaderBytes) continues Read by Read.  It applies where it gives exactly the bytes and errors of
 // Read-by-Read decoding: a clean end of stream (status OK), RequireMagic and SkipUnsupportedMeta off;
 // anything else leaves the handle as it was and the exact decoder runs Read by Read.  Device buffers are
@@ -235,6 +245,8 @@ int hand_history(ez_reader *r, DBuf &to, const uint8_t *end, size_t H2, bool dra
 // served from the decoded bytes.
 int reader_ahead(ez_reader *r, const uint8_t *b, size_t b_len) {
     r->tried = 1;
+    r->w_slot = 0;
+    r->w_launches = 0;
     if (b_len == 0 || b_len > ((size_t)1 << 28) || r->require_magic || r->skip_meta) return 0;
     const size_t ws = ez_decompress_workspace(1);
     constexpr size_t o_meta = 64;  // [in_off 2][out_off 2][out_size][status][end_state 2]
@@ -242,42 +254,65 @@ int reader_ahead(ez_reader *r, const uint8_t *b, size_t b_len) {
         return 0;
     if (!stage_ready(r)) return 0;
     if (hipMemcpyAsync(r->a_in.p, b, b_len, hipMemcpyHostToDevice, r->stream) != hipSuccess) return 0;
-    size_t cap = 8 * b_len + 4096 < kAheadMax ? 8 * b_len + 4096 : kAheadMax;
-    for (;;) {
-        if (r->a_out.ensure(cap + 64)) return 0;
-        uint64_t m[8] = {0, (uint64_t)b_len, 0, (uint64_t)cap, 0, 0, (uint64_t)-1, (uint64_t)-1};
-        uint64_t nbrk = 0;
-        if (hipMemcpyAsync(r->a_meta.p, m, sizeof m, hipMemcpyHostToDevice, r->stream) != hipSuccess) return 0;
-        if (hipMemsetAsync(r->a_brk.p, 0, 8, r->stream) != hipSuccess) return 0;
-        ez::DecompressArgs a = ahead_args(r, r->a_in, r->a_out.as<uint8_t>(), r->a_meta.as<uint64_t>(), r->a_ws, cap);
-        // one stream: K2j (chip-wide) for a long one, else the token-parallel wave
-        a.force = b_len >= ((size_t)16 << 10) ? 'j' : 't';
-        {
-            const auto lk = jws_lease(r, a, a.force == 'j' ? ez::jump_workspace_bytes(1, b_len, cap) : 0);
-            if (!lk) return 0;
-            if (ez::launch_decompress(a, r->stream) != hipSuccess) return 0;
-            if (hipMemcpyAsync(m, r->a_meta.p, sizeof m, hipMemcpyDeviceToHost, r->stream) != hipSuccess) return 0;
-            if (hipMemcpyAsync(&nbrk, r->a_brk.p, 8, hipMemcpyDeviceToHost, r->stream) != hipSuccess) return 0;
-            if (hipStreamSynchronize(r->stream) != hipSuccess) return 0;
+    uint64_t m[8] = {0, (uint64_t)b_len, 0, 0, 0, (uint64_t)(uint32_t)-7, (uint64_t)-1, (uint64_t)-1};
+    if (hipMemcpyAsync(r->a_meta.p, m, sizeof m, hipMemcpyHostToDevice, r->stream) != hipSuccess) return 0;
+    {  // the stream's decoded size and status
+        ez::DecompressArgs q{};
+        uint64_t *dm = r->a_meta.as<uint64_t>();
+        q.in = r->a_in.as<uint8_t>();
+        q.in_off = dm;
+        q.out_size = dm + 4;
+        q.status = (int32_t *)(dm + 5);
+        q.count = 1;
+        q.block_size_limit = r->limit;
+        q.slow = r->a_ws.as<uint32_t>();
+        q.in_bytes = b_len;
+        // (the parts route's scratch is the handle's: a cache entry per handle stream would be allocated
+        // anew for every NewReaderBytes; without it the query takes the wave route)
+        if (!r->a_qws.ensure(ez::size_parts_workspace_bytes(1, b_len))) {
+            q.jws = r->a_qws.p;
+            q.jws_cap = r->a_qws.cap;
+        } else {
+            q.in_bytes = 0;
         }
-        const int status = (int32_t)(m[5] & 0xffffffffu);
-        if ((int64_t)m[6] == -2 && status == EZ_ENOSPC && cap < kAheadMax) {  // the slot was too small
-            cap = cap < kAheadMax / 4 ? 4 * cap : kAheadMax;
-            continue;
-        }
-        if (status != EZ_OK || m[4] > cap || nbrk > kAheadBrk || (int64_t)m[6] < 0) return 0;
-        if (!fetch_breaks(r, nbrk, 0)) return 0;
-        r->brk_next = 0;
-        r->a_n = m[4];
-        r->a_at = 0;
-        r->a_blen = b_len;
-        r->end_bs = (int64_t)m[6];
-        r->end_pos = (int64_t)m[7];
-        r->stage_at = r->stage_n = 0;
-        r->srv = r->a_out.as<uint8_t>();
-        r->ahead_on = 1;
-        return 1;
+        if (ez::launch_decompress_size(q, b_len, r->stream) != hipSuccess) return 0;
+        if (hipMemcpyAsync(m, r->a_meta.p, sizeof m, hipMemcpyDeviceToHost, r->stream) != hipSuccess) return 0;
+        if (hipStreamSynchronize(r->stream) != hipSuccess) return 0;
     }
+    if ((int32_t)(m[5] & 0xffffffffu) != EZ_OK || m[4] > kAheadMax) return 0;
+    const size_t cap = m[4] < 16 ? 16 : (size_t)((m[4] + 15) & ~(uint64_t)15);  // (a fast decoder takes slots of 16 bytes or more)
+    if (r->a_out.ensure(cap + 64)) return 0;
+    r->w_slot = cap;
+    m[3] = cap;
+    m[4] = m[5] = 0;
+    uint64_t nbrk = 0;
+    if (hipMemcpyAsync(r->a_meta.p, m, sizeof m, hipMemcpyHostToDevice, r->stream) != hipSuccess) return 0;
+    if (hipMemsetAsync(r->a_brk.p, 0, 8, r->stream) != hipSuccess) return 0;
+    ez::DecompressArgs a = ahead_args(r, r->a_in, r->a_out.as<uint8_t>(), r->a_meta.as<uint64_t>(), r->a_ws, cap);
+    // one stream: K2j (chip-wide) for a long one, else the token-parallel wave
+    a.force = b_len >= ((size_t)16 << 10) ? 'j' : 't';
+    {
+        const auto lk = jws_lease(r, a, a.force == 'j' ? ez::jump_workspace_bytes(1, b_len, cap) : 0);
+        if (!lk) return 0;
+        r->w_launches++;
+        if (ez::launch_decompress(a, r->stream) != hipSuccess) return 0;
+        if (hipMemcpyAsync(m, r->a_meta.p, sizeof m, hipMemcpyDeviceToHost, r->stream) != hipSuccess) return 0;
+        if (hipMemcpyAsync(&nbrk, r->a_brk.p, 8, hipMemcpyDeviceToHost, r->stream) != hipSuccess) return 0;
+        if (hipStreamSynchronize(r->stream) != hipSuccess) return 0;
+    }
+    const int status = (int32_t)(m[5] & 0xffffffffu);
+    if (status != EZ_OK || m[4] > cap || nbrk > kAheadBrk || (int64_t)m[6] < 0) return 0;
+    if (!fetch_breaks(r, nbrk, 0)) return 0;
+    r->brk_next = 0;
+    r->a_n = m[4];
+    r->a_at = 0;
+    r->a_blen = b_len;
+    r->end_bs = (int64_t)m[6];
+    r->end_pos = (int64_t)m[7];
+    r->stage_at = r->stage_n = 0;
+    r->srv = r->a_out.as<uint8_t>();
+    r->ahead_on = 1;
+    return 1;
 }
 
 // n bytes of the decoded stream from a_at into p (staged; a copy larger than the window goes direct)

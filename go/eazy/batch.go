@@ -266,3 +266,48 @@ func decompressedSizes(streams [][]byte, blockSizeLimit int) ([]uint64, []error,
 	}
 	return sizes, errs, nil
 }
+
+// decompressedSizesMulti: every stream's decoded length without decoding, from host memory over
+// several devices (ez_decompressed_size_batch_multi; devices nil: every visible device).  The call
+// stages, queries and reads back per shard and returns when the lengths are in host memory; its
+// return code covers every HIP call it made, and is checked before any length is used.  A stream's
+// own error is returned as the reference's Reader would report it, with the bytes it produced
+// before it in sizes[k].
+func decompressedSizesMulti(streams [][]byte, blockSizeLimit int, devices []int) ([]uint64, []error, error) {
+	count := len(streams)
+	if count == 0 {
+		return nil, nil, nil
+	}
+	inOff := make([]uint64, count+1)
+	for k, s := range streams {
+		inOff[k+1] = inOff[k] + uint64(len(s))
+	}
+	host := make([]byte, 0, inOff[count]+1)
+	for _, s := range streams {
+		host = append(host, s...)
+	}
+	host = append(host, 0) // (never read: &host[0] must exist for a batch of empty streams)
+	var devs *C.int
+	cdev := make([]C.int, len(devices))
+	for k, d := range devices {
+		cdev[k] = C.int(d)
+	}
+	if len(cdev) > 0 {
+		devs = &cdev[0]
+	}
+	sizes := make([]uint64, count)
+	status := make([]int32, count)
+	st := C.ez_decompressed_size_batch_multi(C.int64_t(blockSizeLimit), (*C.uint8_t)(unsafe.Pointer(&host[0])),
+		(*C.uint64_t)(unsafe.Pointer(&inOff[0])), C.uint64_t(count), devs, C.int(len(cdev)),
+		(*C.uint64_t)(unsafe.Pointer(&sizes[0])), (*C.int32_t)(unsafe.Pointer(&status[0])))
+	if st != C.EZ_OK {
+		return nil, nil, toErr(st, 0)
+	}
+	errs := make([]error, count)
+	for k := range streams {
+		if status[k] != 0 {
+			errs[k] = toErr(C.int(status[k]), 0)
+		}
+	}
+	return sizes, errs, nil
+}

@@ -178,6 +178,12 @@ int ez_reader_pending(const ez_reader *r); /* r.state != 0 (reader.go:135) */
 int ez_reader_set_whole(ez_reader *r, int whole);
 /* 1 when this stream's Reads are being served from the whole-stream decode (tests, measurement). */
 int ez_reader_whole_decoded(const ez_reader *r);
+/* Introspection (tests, measurement) of the last whole-stream attempt (the first Read of a set_whole
+ * handle): the capacity in bytes of the slot it decoded into (the stream's decoded size from the size
+ * query, rounded up to 16; 0 if it decoded nothing: the query gave an error or a size over 1 GiB, and
+ * the Reads are decoded one by one), and the number of decode launches it made (0 or 1). */
+uint64_t ez_reader_whole_slot(const ez_reader *r);
+int ez_reader_whole_launches(const ez_reader *r);
 /* NewReader(io.Reader) handles (set_whole 0) read ahead: a Read with nothing decoded ahead and at
  * least 8 KiB of buffered input b[i..b_len) decodes every whole token of it at once on the device
  * (K2j continuing the stream from the handle's state, a literal the buffer ends inside of decoded as
@@ -271,14 +277,23 @@ int ez_decompress_batch(int64_t block_size_limit, const ez_batch *b, void *works
  * skipped; for a stream that ends in an error, the bytes produced before it), status[s] = EZ_OK or
  * that first error.  Uses b->in, in_off, out_size (required), status (may be NULL), count and
  * max_len (host hint: the longest INPUT stream in bytes, 0 = unknown; it picks the chunk size and
- * nothing else: any value gives the same results).  b->out, out_off, in_bytes, out_bytes are
- * ignored (out and out_off may be NULL).  workspace >= ez_decompress_workspace(count) enables the
+ * nothing else: any value gives the same results) and in_bytes (host hint: in_off[count] -
+ * in_off[0], 0 = unknown; it enables the parts route below and nothing else: any value gives the
+ * same results).  b->out, out_off and out_bytes are ignored (out and out_off may be NULL).  workspace >= ez_decompress_workspace(count) enables the
  * fast kernel (streams it cannot take go to the exact decoder run dry); NULL = exact decoder only.
  * The fast kernel is a wave per stream, or, for 4,096 streams or more of at most 4 KiB (max_len), a
- * lane per stream.  Asynchronous on hip_stream; never waits for the stream.  Reads in[0 .. in_off[count]) as
+ * lane per stream; or the parts route: every stream's token chain cut on a fixed grid of parts of 64
+ * chunks, a wave per part and then a wave per stream that follows the true chain through the parts'
+ * records and walks again only the parts it enters elsewhere.  The parts route sizes its records from
+ * in_bytes, so it runs only where the caller gives in_bytes (and the route is selected, see
+ * ez_select_size_route); a kernel checks the real extent against the hint before anything indexes
+ * those records, and an under-stated hint leaves the whole batch to the wave route (an over-stated one
+ * only enlarges the scratch, which is kept per (device, HIP stream) and freed by ez_release_cached;
+ * if it cannot be had the call takes the wave route).  Asynchronous on hip_stream; never waits for the stream.  Reads in[0 .. in_off[count]) as
  * ez_decompress_batch does; writes only out_size[0..count), status[0..count) and the workspace.
  * Sizes are 64-bit throughout: an output over 4 GiB is reported, not clamped.
- * Held by tests/test_gpu_k2z.py and tests/test_k2_size.py. */
+ * Held by tests/test_gpu_k2z.py, tests/test_k2_size.py, tests/test_gpu_k2z_parts.py and
+ * tests/test_k2_size_parts.py. */
 int ez_decompressed_size_batch(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
 /* Introspection (tests, tuning): the chunk bytes the fast kernel takes for a max_len hint (host function). */
 int ez_decompressed_size_chunk(uint64_t max_len);
@@ -286,6 +301,17 @@ int ez_decompressed_size_chunk(uint64_t max_len);
  * 1: the lane-per-stream kernel, which batches of 4,096 streams or more take when max_len says they
  * are at most 4 KiB each: no chunks) */
 int ez_decompressed_size_chunk_last(void);
+/* Testing / A-B measurement: the fast route of later ez_decompressed_size_batch calls in this
+ * process: 'p' the parts route at any stream length (it still needs b->in_bytes; chunk 1,024 where
+ * the wave route takes 1,024, else 256), 'v' never the parts route, 0 = automatic.  EZ_EINVAL for
+ * any other value.  Not thread-safe against concurrent calls. */
+int ez_select_size_route(int kind);
+/* Introspection (tests, measurement): of the last ez_decompressed_size_batch call of this process,
+ * counts[0] = parts the parts route walked in its first pass, counts[1] = parts whose record the
+ * true chain took as it stood, counts[2] = parts walked again from the true entry (parts a token
+ * spans are in neither); all 0 where the parts route did not run or found in_bytes too small.  The
+ * caller has synchronised that call's stream; the call reads the counters back from the device. */
+int ez_decompressed_size_parts_last(uint64_t counts[3]);
 
 /* ---- host-memory batches over several devices (SURVEY §8b device_or_all) ----
  * Streams share no state (writer.go:40-45, reader.go:17-40), so a batch splits into contiguous
@@ -308,6 +334,14 @@ int ez_compress_batch_multi(int64_t block, int64_t htable, int flags, const uint
 int ez_decompress_batch_multi(int64_t block_size_limit, const uint8_t *in, const uint64_t *in_off, uint64_t count,
                               const int *devices, int ndev, uint8_t *out, const uint64_t *out_off, uint64_t *out_size,
                               int32_t *status);
+/* Decoded sizes: what ez_decompress_batch_multi would report for every stream given slots that are
+ * large enough, without decoding and without an output (ez_decompressed_size_batch on every shard,
+ * with each shard's max_len and in_bytes hints): out_size[count] and status[count] (may be NULL).
+ * A caller that does not know its decoded lengths lays its slots out from out_size (a host prefix
+ * sum) and then calls ez_decompress_batch_multi.  EZ_EINVAL for NULL in_off or out_size (checked
+ * before any device use); count == 0 returns EZ_OK. */
+int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in, const uint64_t *in_off, uint64_t count,
+                                     const int *devices, int ndev, uint64_t *out_size, int32_t *status);
 
 /* Frees the device scratch kept between batch calls (no reference counterpart; a caching
  * allocator's empty_cache): K1 / K1c scratch and K2j workspaces per (device, HIP stream), the
