@@ -7,7 +7,9 @@ This module is a thin ctypes layer over it:
   (writer.go:17-46, reader.go:17-40) with the same field names, flush policy
   and error values; their compression / decompression runs on the GPU.
 * ``compress_batch`` / ``pack`` / ``decompress_batch`` drive the batched,
-  device-resident kernels (K1/K3/K2) on torch CUDA tensors.
+  device-resident kernels (K1/K3/K2) on torch CUDA tensors;
+  ``stream_segments`` / ``decompress_batch_segmented`` (K2g) take batches of
+  concatenated streams.
 * ``Encoder`` / ``Decoder`` expose the token codec (writer.go:537-621,
   reader.go:346-514).
 
@@ -134,6 +136,12 @@ def _lib():
     L.ez_decompress_batch.argtypes = [i64, vp, vp, vp]
     L.ez_decompressed_size_batch.argtypes = [i64, vp, vp, vp]
     L.ez_decompressed_size_chunk.argtypes = [C.c_uint64]
+    L.ez_segments_workspace.restype = sz
+    L.ez_segments_workspace.argtypes = [C.c_uint64]
+    L.ez_stream_segments_batch.argtypes = [i64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
+    L.ez_segments_merge_batch.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ez_decompress_batch_segmented.argtypes = [i64, vp, vp, vp]
+    L.ez_segments_last.argtypes = [C.POINTER(C.c_uint64)]
     _L = L
     return L
 
@@ -976,6 +984,76 @@ def decompressed_sizes(comp, comp_off, block_size_limit: int = 0, sizes=None, st
     ws = None if exact_only else workspace.data_ptr()
     _check(_lib().ez_decompressed_size_batch(block_size_limit, C.byref(b), ws, _stream_ptr(stream)))
     return sizes, status
+
+
+def stream_segments(comp, comp_off, out_off, block_size_limit: int = 0, seg_cap: int | None = None, max_len: int = 0,
+                    stream=None):
+    """K2g: where the streams comp[comp_off[s]:comp_off[s+1]] can be cut at a MetaReset after output
+    (concatenated streams, a Writer that was Reset) -> (seg_idx, seg_in, seg_out, seg_total), int64
+    CUDA tensors.  Stream s owns the segments seg_idx[s] .. seg_idx[s+1]-1; segment g is
+    comp[seg_in[g]:seg_in[g+1]] decoded into out[seg_out[g]:seg_out[g+1]] (out_off[s] plus the output
+    before the cut, clamped to out_off[s+1]); a segment decodes as a stream of its own, and a stream the
+    query does not understand keeps everything after its last good cut in one segment.  seg_total =
+    (segments written, segments found).  seg_cap: room for that many segments; more found gives one
+    segment per stream and seg_total = (count, found).  None: some room, and where it was too little
+    the call reads seg_total back (which waits for the stream) and asks again with enough.  max_len is
+    an optional host hint, the longest INPUT stream in bytes: it picks the chunk size and nothing else.
+    Asynchronous on the stream when seg_cap is given."""
+    import torch
+
+    _need_cuda(comp, comp_off, out_off)
+    count = comp_off.numel() - 1
+    dev = comp.device
+    L = _lib()
+    cap = 2 * count + 64 if seg_cap is None else seg_cap  # (seg_cap < count: the library refuses it)
+    ws = torch.empty(L.ez_segments_workspace(count), dtype=torch.uint8, device=dev)
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, out_off.data_ptr(), None, None, count, max_len, 0, 0)
+    seg_idx = torch.empty(count + 1, dtype=torch.int64, device=dev)
+    seg_total = torch.empty(2, dtype=torch.int64, device=dev)
+    while True:
+        seg_in = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+        seg_out = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+        _check(L.ez_stream_segments_batch(block_size_limit, C.byref(b), seg_idx.data_ptr(), seg_in.data_ptr(), seg_out.data_ptr(), cap,
+                                          seg_total.data_ptr(), ws.data_ptr(), _stream_ptr(stream)))
+        if seg_cap is not None:
+            break
+        written, found = (int(v) for v in seg_total.cpu())
+        if found <= written:
+            seg_in, seg_out = seg_in[: written + 1], seg_out[: written + 1]
+            break
+        cap = found
+    return seg_idx, seg_in, seg_out, seg_total
+
+
+def decompress_batch_segmented(comp, comp_off, out_off, block_size_limit: int = 0, out=None, sizes=None, status=None, stream=None):
+    """decompress_batch for batches whose streams may be concatenated (a MetaReset after output: a
+    Writer that was Reset, streams joined back to back) -> (out, sizes, status), the same results with
+    every segment on the fast decoders: stream_segments into the library's own scratch, one read-back
+    (which waits for the stream), the batch decoders over the segments, and the per-stream merge of
+    their sizes and statuses.  A batch without such a Reset costs the query and then decompress_batch's
+    decode."""
+    import torch
+
+    _need_cuda(comp, comp_off, out_off)
+    count = comp_off.numel() - 1
+    dev = comp.device
+    if out is None:
+        out = torch.empty(int(out_off[-1].item()) + 16, dtype=torch.uint8, device=dev)
+    if sizes is None:
+        sizes = torch.empty(count, dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(count, dtype=torch.int32, device=dev)
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), out.data_ptr(), out_off.data_ptr(), sizes.data_ptr(), status.data_ptr(), count, 0, 0, 0)
+    _check(_lib().ez_decompress_batch_segmented(block_size_limit, C.byref(b), None, _stream_ptr(stream)))
+    return out, sizes, status
+
+
+def segments_last() -> tuple[int, int, int]:
+    """Of the last decompress_batch_segmented call, after its stream was synchronised: segments
+    decoded, how many of them the fast decoders handed to the exact decoder, query retries."""
+    c = (C.c_uint64 * 3)()
+    _check(_lib().ez_segments_last(c))
+    return int(c[0]), int(c[1]), int(c[2])
 
 
 def decompress_batch_sized(comp, comp_off, block_size_limit: int = 0, stream=None):

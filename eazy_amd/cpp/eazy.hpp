@@ -761,6 +761,29 @@ inline Err DecompressedSizeBatch(int64_t block_size_limit, const ez_batch &b, vo
     if (st == EZ_EINVAL) throw std::invalid_argument("eazy: DecompressedSizeBatch: out_size is required");
     return (Err)st;
 }
+// ez_stream_segments_batch (K2g): where the streams of b can be cut at a MetaReset after output
+// (concatenated streams, a Writer that was Reset).  Stream s owns the segments seg_idx[s] ..
+// seg_idx[s+1]-1; segment g is in[seg_in[g] .. seg_in[g+1]) decoded into out[seg_out[g] .. seg_out[g+1]);
+// seg_total = {segments written, segments found} (more found than seg_cap: one segment per stream).
+// Device arrays: seg_idx[count+1], seg_in and seg_out[seg_cap+1], seg_total[2], workspace of
+// ez_segments_workspace(count) bytes; b.max_len is the longest INPUT stream (0: unknown).
+inline Err StreamSegments(int64_t block_size_limit, const ez_batch &b, uint64_t *seg_idx, uint64_t *seg_in, uint64_t *seg_out,
+                          uint64_t seg_cap, uint64_t *seg_total, void *workspace, void *hip_stream) {
+    const int st = ez_stream_segments_batch(block_size_limit, &b, seg_idx, seg_in, seg_out, seg_cap, seg_total, workspace, hip_stream);
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: StreamSegments: a null array, or seg_cap < count");
+    return (Err)st;
+}
+// ez_decompress_batch_segmented: DecompressBatch for batches whose streams may be concatenated, with
+// every segment on the fast decoders; the same out, out_size and status.  It keeps its own scratch
+// and waits for the stream once (the read-back of the segment count).
+inline Err DecompressBatchSegmented(int64_t block_size_limit, const ez_batch &b, void *hip_stream) {
+    const int st = ez_decompress_batch_segmented(block_size_limit, &b, nullptr, hip_stream);
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: DecompressBatchSegmented: in_off, out_off and out_size are required");
+    return (Err)st;
+}
+// ez_segments_last: of the last DecompressBatchSegmented call, {segments decoded, handed to the exact
+// decoder, query retries}
+inline Err SegmentsLast(uint64_t counts[3]) { return (Err)ez_segments_last(counts); }
 
 // Host-memory batches over several devices (ez_compress_batch_multi / ez_decompress_batch_multi):
 // bufs[k] is one Write to a fresh NewWriter(block, htable); out[k] gets its compressed bytes,

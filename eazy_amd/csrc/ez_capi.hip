@@ -320,10 +320,68 @@ extern "C" int ez_decompressed_size_parts_last(uint64_t counts[3]) {
     return EZ_OK;
 }
 
+// ---- K2g: concatenated streams (ez_decompress_segs.hip)
+
+extern "C" size_t ez_segments_workspace(uint64_t count) { return (size_t)ez::segments_workspace_bytes(count); }
+
+extern "C" int ez_stream_segments_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *seg_idx, uint64_t *seg_in, uint64_t *seg_out,
+                                        uint64_t seg_cap, uint64_t *seg_total, void *workspace, void *hip_stream) {
+    if (!b || !b->in_off || !b->out_off || !seg_idx || !seg_in || !seg_out || !seg_total || !workspace) return EZ_EINVAL;
+    if ((b->count != 0 && !b->in) || seg_cap < b->count) return EZ_EINVAL;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    ez::SegsArgs a{};
+    a.in = b->in;
+    a.in_off = b->in_off;
+    a.out_off = b->out_off;
+    a.count = b->count;
+    a.block_size_limit = block_size_limit;
+    a.seg_idx = seg_idx;
+    a.seg_in = seg_in;
+    a.seg_out = seg_out;
+    a.seg_cap = seg_cap;
+    a.seg_total = seg_total;
+    EZ_HIP(ez::launch_segments(a, b->max_len, workspace, (hipStream_t)hip_stream));
+    return EZ_OK;
+}
+
+extern "C" int ez_segments_merge_batch(const ez_batch *b, const uint64_t *seg_idx, const uint64_t *seg_out, const uint64_t *seg_size,
+                                       const int32_t *seg_status, void *hip_stream) {
+    if (!b || !b->out_off || !b->out_size || !seg_idx || !seg_out || !seg_size || !seg_status) return EZ_EINVAL;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    EZ_HIP(ez::launch_segments_merge(b->out_off, b->out_size, b->status, b->count, seg_idx, seg_out, seg_size, seg_status, nullptr, nullptr,
+                                     (hipStream_t)hip_stream));
+    return EZ_OK;
+}
+
+extern "C" int ez_decompress_batch_segmented(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream) {
+    (void)workspace;  // (accepted for symmetry with ez_decompress_batch: the call keeps its own)
+    if (!b || !b->in_off || !b->out_off || !b->out_size) return EZ_EINVAL;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    ez::DecompressArgs a{};
+    a.in = b->in;
+    a.in_off = b->in_off;
+    a.out = b->out;
+    a.out_off = b->out_off;
+    a.out_size = b->out_size;
+    a.status = b->status;
+    a.count = b->count;
+    a.block_size_limit = block_size_limit;
+    EZ_HIP(ez::launch_decompress_segmented(a, (hipStream_t)hip_stream));
+    return EZ_OK;
+}
+
+extern "C" int ez_segments_last(uint64_t counts[3]) {
+    if (!counts) return EZ_EINVAL;
+    counts[0] = counts[1] = counts[2] = 0;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    EZ_HIP(ez::segments_last(counts));
+    return EZ_OK;
+}
+
 // Frees the device scratch the batch calls keep between calls (no reference counterpart; like a
 // caching allocator's empty_cache): the K1 / K1c scratch and K2j workspaces per (device, HIP stream),
-// the multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace and
-// ez_writer_write_many's staging, on `device` (< 0: every device).  Scratch a call is using at that moment is kept.
+// the multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace,
+// ez_writer_write_many's staging and ez_decompress_batch_segmented's scratch, on `device` (< 0: every device).  Scratch a call is using at that moment is kept.
 extern "C" int ez_release_cached(int device) {
     const int have = device_count();
     if (have <= 0) return EZ_EDEVICE;
@@ -334,6 +392,7 @@ extern "C" int ez_release_cached(int device) {
         k1_cache().trim(d);
         ez::jump_cache().trim(d);
         ez::size_cache().trim(d);
+        ez::segs_cache().trim(d);
         reader_release_cached(d);
         writer_release_cached(d);
     }

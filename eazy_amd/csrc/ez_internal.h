@@ -249,6 +249,40 @@ void select_size_route(int v);     // 0 = automatic, 'p' parts at any length, 'v
 int selected_size_route();
 void size_parts_none();            // the last query did not take the parts route
 hipError_t size_parts_last(uint64_t counts[3]);  // parts launched, taken as recorded, walked again
+// K2g, the segment query (ez_decompress_segs.hip): where each stream can be cut at a MetaReset after
+// output.  Stream s owns the segments seg_idx[s] .. seg_idx[s+1]-1; segment g is in[seg_in[g] ..
+// seg_in[g+1]) decoded into out[seg_out[g] .. seg_out[g+1]) (out_off[s] plus the output before the cut,
+// clamped to out_off[s+1]); seg_total = {segments written, segments found}: more found than seg_cap
+// gives one segment per stream
+struct SegsArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;   // count+1
+    const uint64_t *out_off;  // count+1
+    uint64_t count;
+    int64_t block_size_limit;
+    uint64_t *seg_idx;        // count+1
+    uint64_t *seg_in;         // seg_cap+1
+    uint64_t *seg_out;        // seg_cap+1
+    uint64_t seg_cap;         // >= count
+    uint64_t *seg_total;      // 2
+    uint32_t *hdr;            // the workspace's header and the cuts the count pass keeps (set by the launcher)
+    uint64_t *keep;
+};
+uint64_t segments_workspace_bytes(uint64_t count);
+// max_len: the caller's hint, the longest input stream (0 = unknown), which picks the chunk (size_chunk)
+hipError_t launch_segments(const SegsArgs &a, uint64_t max_len, void *workspace, hipStream_t s);
+// per stream its first segment whose status is not EZ_OK, else its last: out_size[s] = seg_out[g] -
+// out_off[s] + seg_size[g], status[s] (may be null) = seg_status[g]; slow, handed (optional): *handed =
+// slow[0], the segments the fast decoders handed over
+hipError_t launch_segments_merge(const uint64_t *out_off, uint64_t *out_size, int32_t *status, uint64_t count, const uint64_t *seg_idx,
+                                 const uint64_t *seg_out, const uint64_t *seg_size, const int32_t *seg_status, const uint32_t *slow,
+                                 uint64_t *handed, hipStream_t s);
+// the query into scratch kept per (device, HIP stream), one read-back (which waits for the stream),
+// launch_decompress over the segments, the merge; uses a's in, in_off, out, out_off, out_size, status,
+// count and block_size_limit.  (hipErrorOutOfMemory: the scratch could not be had)
+hipError_t launch_decompress_segmented(const DecompressArgs &a, hipStream_t s);
+DevCache &segs_cache();
+hipError_t segments_last(uint64_t counts[3]);  // of the last segmented decode: segments, handed over, query retries
 bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once, ez_k1_probe.hip)
 bool lds_mskor_in_lane_order();     // the LDS property k1_lean's one-atomic visit relies on (checked once)
 hipError_t launch_pack(const uint8_t *slots, const uint64_t *slot_off, const uint64_t *sizes, uint64_t count,

@@ -311,3 +311,100 @@ func decompressedSizesMulti(streams [][]byte, blockSizeLimit int, devices []int)
 	}
 	return sizes, errs, nil
 }
+
+// DecompressBatchSegmented decodes independent streams that may each be several streams joined back
+// to back, or the output of a Writer that was Reset (a MetaReset after output), on the GPU
+// (ez_decompress_batch_segmented): the segment query cuts every stream at such Resets and the batch
+// decoders take one segment each.  caps[k] is the room for stream k's output; the result for
+// streams[k] is what NewReaderBytes(streams[k]) read to EOF produces, with the Reader's error in
+// errs[k] (EZ_ENOSPC's error where caps[k] is too small).  The streams are staged into device
+// memory, the call runs on the null stream, and the outputs, lengths and statuses come back; every
+// HIP call's result is checked before anything is used.
+func DecompressBatchSegmented(streams [][]byte, caps []uint64, blockSizeLimit int) ([][]byte, []error, error) {
+	count := len(streams)
+	if count == 0 {
+		return nil, nil, nil
+	}
+	if len(caps) != count {
+		return nil, nil, toErr(C.EZ_EINVAL, 0)
+	}
+	inOff := make([]uint64, count+1)
+	outOff := make([]uint64, count+1)
+	for k, s := range streams {
+		inOff[k+1] = inOff[k] + uint64(len(s))
+		outOff[k+1] = outOff[k] + caps[k]
+	}
+	host := make([]byte, 0, inOff[count])
+	for _, s := range streams {
+		host = append(host, s...)
+	}
+	var dIn, dOut, dInOff, dOutOff, dSize, dStatus unsafe.Pointer
+	defer func() {
+		for _, p := range []unsafe.Pointer{dIn, dOut, dInOff, dOutOff, dSize, dStatus} {
+			if p != nil {
+				C.hipFree(p)
+			}
+		}
+	}()
+	// every HIP call's result is checked: a failed copy must never hand back stale bytes as success
+	hip := func(r C.hipError_t) error {
+		if r != C.hipSuccess {
+			return ErrDevice
+		}
+		return nil
+	}
+	for _, a := range []struct {
+		p *unsafe.Pointer
+		n uint64
+	}{{&dIn, inOff[count]}, {&dOut, outOff[count]}, {&dInOff, 8 * uint64(count+1)}, {&dOutOff, 8 * uint64(count+1)},
+		{&dSize, 8 * uint64(count)}, {&dStatus, 4 * uint64(count)}} {
+		if err := hip(C.hipMalloc(a.p, C.size_t(a.n+16))); err != nil {
+			return nil, nil, err
+		}
+	}
+	if len(host) > 0 {
+		if err := hip(C.hipMemcpy(dIn, unsafe.Pointer(&host[0]), C.size_t(len(host)), C.hipMemcpyHostToDevice)); err != nil {
+			return nil, nil, err
+		}
+	}
+	if err := hip(C.hipMemcpy(dInOff, unsafe.Pointer(&inOff[0]), C.size_t(8*(count+1)), C.hipMemcpyHostToDevice)); err != nil {
+		return nil, nil, err
+	}
+	if err := hip(C.hipMemcpy(dOutOff, unsafe.Pointer(&outOff[0]), C.size_t(8*(count+1)), C.hipMemcpyHostToDevice)); err != nil {
+		return nil, nil, err
+	}
+	b := C.ez_batch{
+		in: (*C.uint8_t)(dIn), in_off: (*C.uint64_t)(dInOff), out: (*C.uint8_t)(dOut), out_off: (*C.uint64_t)(dOutOff),
+		out_size: (*C.uint64_t)(dSize), status: (*C.int32_t)(dStatus), count: C.uint64_t(count),
+	}
+	if st := C.ez_decompress_batch_segmented(C.int64_t(blockSizeLimit), &b, nil, nil); st != C.EZ_OK {
+		return nil, nil, toErr(st, 0)
+	}
+	out := make([]byte, outOff[count]+1)
+	size := make([]uint64, count)
+	status := make([]int32, count)
+	// (hipMemcpy to host waits for the call's kernels on the null stream, and reports their faults)
+	if outOff[count] > 0 {
+		if err := hip(C.hipMemcpy(unsafe.Pointer(&out[0]), dOut, C.size_t(outOff[count]), C.hipMemcpyDeviceToHost)); err != nil {
+			return nil, nil, err
+		}
+	}
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&size[0]), dSize, C.size_t(8*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, err
+	}
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&status[0]), dStatus, C.size_t(4*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, err
+	}
+	res := make([][]byte, count)
+	errs := make([]error, count)
+	for k := range streams {
+		if size[k] > caps[k] {
+			return nil, nil, ErrDevice // (never: a size is at most its slot)
+		}
+		res[k] = out[outOff[k] : outOff[k]+size[k] : outOff[k]+size[k]]
+		if status[k] != 0 {
+			errs[k] = toErr(C.int(status[k]), 0)
+		}
+	}
+	return res, errs, nil
+}

@@ -313,6 +313,61 @@ int ez_select_size_route(int kind);
  * caller has synchronised that call's stream; the call reads the counters back from the device. */
 int ez_decompressed_size_parts_last(uint64_t counts[3]);
 
+/* K2g: concatenated streams.  A stream may hold a MetaReset after output (reader.go:305-311, 327-344: a
+ * Writer that was Reset, or streams joined back to back); ez_decompress_batch hands such a stream to
+ * the exact decoder whole.  Reader.reset zeroes the block and sets r.pos = 0, so the stream is as many
+ * independent streams as it has such Resets, plus one, and this query finds them: a *cut* is a
+ * MetaReset on the stream's token chain with output before it in the stream (Resets before the first
+ * output byte stay in segment 0; a Reset with no output since the previous cut is still a cut: empty
+ * segments are allowed).  A cut is recorded only if the segment it closes would be taken by the fast
+ * decoders (no form they hand over, a window set before its first token, its longest distance within
+ * its window); at the first segment that is not, and for a stream of 2 GiB or more, the walk of that
+ * stream stops: the cuts so far stand and the rest of the stream is its last segment, which the
+ * decoders then see exactly as they see the whole stream today.
+ * Stream s owns the segments seg_idx[s] .. seg_idx[s+1]-1 (seg_idx[count+1]); segment g is
+ * in[seg_in[g] .. seg_in[g+1]) decoded into out[seg_out[g] .. seg_out[g+1]) (absolute offsets in the
+ * style of in_off / out_off, seg_cap+1 entries each).  seg_in[seg_idx[s]] = in_off[s]; a cut's seg_in
+ * is the position of the Reset's 0x80 tag byte (padding before it belongs to the segment before);
+ * its seg_out is out_off[s] plus the output before the cut, clamped to out_off[s+1] (a stream whose
+ * slot is too small ends in segments of short or zero capacity).  Both arrays end at in_off[count]
+ * and out_off[count].  seg_total[0] = the segments written, seg_total[1] = the segments found: where
+ * those exceed seg_cap the one-segment-per-stream layout is written instead (seg_idx[s] = s, the
+ * offsets equal to in_off / out_off) and seg_total = {count, found}, so that a caller can retry with room.
+ * Uses b->in, in_off, out_off, count and max_len (host hint: the longest INPUT stream in bytes, 0 =
+ * unknown; it picks the chunk size and nothing else).  workspace >= ez_segments_workspace(count)
+ * device bytes.  EZ_EINVAL for a NULL array or workspace or seg_cap < count; count == 0 writes
+ * seg_idx[0], seg_in[0], seg_out[0] and seg_total and returns EZ_OK.
+ * Asynchronous on hip_stream; never waits for the stream.  Memory touched: reads in[0 .. in_off[count])
+ * as ez_decompress_batch does, in_off and out_off; no output buffer is needed; writes only
+ * seg_idx[0 .. count], seg_in and seg_out[0 .. seg_total[0]], seg_total[0 .. 1] and the workspace.
+ * Held by tests/test_k2_segments.py and tests/test_gpu_segments.py. */
+size_t ez_segments_workspace(uint64_t count);
+int ez_stream_segments_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *seg_idx, uint64_t *seg_in, uint64_t *seg_out,
+                             uint64_t seg_cap, uint64_t *seg_total, void *workspace, void *hip_stream);
+/* The results of a decode over segments, per stream: g = the stream's first segment whose
+ * seg_status is not EZ_OK, else its last; out_size[s] = seg_out[g] - out_off[s] + seg_size[g],
+ * status[s] (may be NULL) = seg_status[g].  Uses b->out_off, out_size, status and count.
+ * Asynchronous on hip_stream.  Memory touched: reads out_off[0 .. count), seg_idx[0 .. count] and the
+ * three segment arrays up to seg_idx[count]; writes only out_size[0 .. count) and status[0 .. count). */
+int ez_segments_merge_batch(const ez_batch *b, const uint64_t *seg_idx, const uint64_t *seg_out, const uint64_t *seg_size,
+                            const int32_t *seg_status, void *hip_stream);
+/* ez_decompress_batch for batches whose streams may be concatenated: the same out, out_size and status,
+ * with every segment on the fast decoders.  In order: ez_stream_segments_batch into scratch the
+ * library keeps per (device, HIP stream) (freed by ez_release_cached); one read-back of seg_total and
+ * the decode's hints, WHICH WAITS FOR THE STREAM; the query once more where the segments found exceeded
+ * the room; ez_decompress_batch's decoders over the segments, with the library's own workspace (always
+ * the fast decoders first); ez_segments_merge_batch.  A batch without any Reset after output costs the
+ * query and then exactly ez_decompress_batch's decode.  Uses b->in, in_off, out, out_off, out_size
+ * (required), status (may be NULL) and count; max_len, in_bytes and out_bytes are ignored (the call
+ * measures them).  workspace is accepted for symmetry and may be NULL.
+ * Memory touched: as ez_decompress_batch; nothing outside the slots, out_size and status is written. */
+int ez_decompress_batch_segmented(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
+/* Introspection (tests, measurement): of the last ez_decompress_batch_segmented call of this process,
+ * counts[0] = segments decoded, counts[1] = how many of them the fast decoders handed to the exact
+ * decoder, counts[2] = query retries.  The caller has synchronised that call's stream; the call reads
+ * counts[1] back from the library's scratch (0 once ez_release_cached freed it). */
+int ez_segments_last(uint64_t counts[3]);
+
 /* ---- host-memory batches over several devices (SURVEY §8b device_or_all) ----
  * Streams share no state (writer.go:40-45, reader.go:17-40), so a batch splits into contiguous
  * whole-stream shards, balanced by bytes, one per entry of `devices` (ndev entries; NULL or 0 =
@@ -345,7 +400,8 @@ int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in
 
 /* Frees the device scratch kept between batch calls (no reference counterpart; a caching
  * allocator's empty_cache): K1 / K1c scratch and K2j workspaces per (device, HIP stream), the
- * multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace; device < 0 =
+ * multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace,
+ * ez_decompress_batch_segmented's scratch; device < 0 =
  * every device.  Scratch in use by a concurrent call is kept.  Entries beyond 8 streams per device
  * are also freed least recently used first as new streams arrive. */
 int ez_release_cached(int device);

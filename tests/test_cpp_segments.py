@@ -1,0 +1,34 @@
+"""The C++ mirror of the segmented decode (eazy::DecompressBatchSegmented, eazy_amd/cpp/eazy.hpp):
+tests/cpp/segments_test.cpp round-trips 64 streams of 4 joined streams each and reads the segment
+counts back; compiled as tests/cpp/Makefile compiles eazy_test."""
+
+import os
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CPP = os.path.join(HERE, "cpp")
+
+
+def _build():
+    exe, src = os.path.join(CPP, "segments_test"), os.path.join(CPP, "segments_test.cpp")
+    deps = [src, os.path.join(ROOT, "eazy_amd", "cpp", "eazy.hpp"), os.path.join(ROOT, "include", "eazy.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        libdir = os.path.join(ROOT, "eazy_amd")
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        p = subprocess.run([hipcc, "-O2", "-std=c++17", "-Wall", "-o", exe, src, f"-L{libdir}", "-leazy_amd", f"-Wl,-rpath,{libdir}"],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+    return exe
+
+
+def test_cpp_segments_compiles():
+    _build()
+
+
+@pytest.mark.gpu
+def test_cpp_segments_round_trip(cuda):
+    p = subprocess.run([_build()], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "segments ok" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
