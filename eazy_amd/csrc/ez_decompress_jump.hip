@@ -415,7 +415,7 @@ __global__ __launch_bounds__(64) void kj_tok(DecompressArgs A, JWork W) {
     const JStage S = kj_stage(A, live, b0 + (uint64_t)c0, b0 + (uint64_t)ce, stage);
     if (!live) return;
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     int32_t p = (int32_t)W.entry[c];
     uint32_t n = 0, fl = 0, maxd = 0;
     uint64_t out = 0;

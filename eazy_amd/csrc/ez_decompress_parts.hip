@@ -8,8 +8,8 @@
 //             leaves the gate closed: the next two kernels do nothing.  The wave route, launched
 //             behind them with the gate and the layout as arguments, sizes every stream if the
 //             gate is closed, else the streams without parts;
-//   kp_first  a wave per part, grid-stride: stage the part and the warm-up chunk before it in LDS,
-//             speculate, verify and repair, sum, reduce, and write the part's record;
+//   kp_first  a wave per part, grid-stride: kz_walk (ez_k2_walk.h) over the part with the warm-up chunk
+//             before it, then sum, reduce, and write the part's record;
 //   kp_order  a wave per stream: follows the true chain through the records, 64 of them per load,
 //             walks again the parts whose record starts elsewhere, and ends as the wave route does:
 //             out_size[s] and EZ_OK, or the stream on the slow list for the exact decoder run dry.
@@ -23,7 +23,7 @@
 #include "ez_cache.h"
 #include "ez_internal.h"
 #include "ez_k2_parts.h"
-#include "ez_wave.h"
+#include "ez_k2_walk.h"
 
 namespace ez {
 namespace {
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kInitThreads) void kp_init(DecompressArgs A, uint32
         if (probe && parts) {
             const uint8_t *b = A.in + A.in_off[s];
             const uint32_t nb = (uint32_t)nb64;
-            if (kp_probe_wave([=](uint32_t p) { return p + 16 <= nb ? ld16v(b + p) : ld_clamped(b + p, b, b + nb); }, nb)) parts = 0;
+            if (kp_probe_wave(kz_global_at(b, nb), nb)) parts = 0;
         }
         base[s] = parts;
         n += parts;
@@ -81,57 +81,20 @@ template <int C>
 __device__ KpRec part_walk(uint8_t *stage, uint32_t (*bm)[C / 32 + 1], const uint8_t *b, uint32_t nb, uint32_t ps, bool known, uint32_t e,
                            int32_t lim32, int64_t limit) {
     const int lane = lane_id();
-    __syncthreads();  // (the previous part's reads are done)
     const uint32_t sbase = kp_stage_base(ps, C);
-    const uint32_t pe = nb - ps > kp_part_bytes(C) ? ps + kp_part_bytes(C) : nb;
-    const uint32_t need = pe + 16 - sbase;  // (at most kp_stage_bytes(C), a multiple of 16)
-    for (uint32_t o = (uint32_t)lane * 16; o < need; o += kWave * 16) {
-        const uint32_t y = sbase + o;
-        V16 v{0, 0};
-        if (y + 16 <= nb) v = ld16v(b + y);
-        else if (y < nb) v = ld_clamped(b + y, b, b + nb);
-        typedef uint64_t __attribute__((aligned(8))) u64a;
-        *(u64a *)(stage + o) = v.lo;
-        *(u64a *)(stage + o + 8) = v.hi;
-    }
-    __syncthreads();
-    const KzWin w{stage, sbase};
-    uint32_t first;
-    const uint32_t sexit = kp_spec<C>(w, ps, lane, nb, known, e, bm[lane], first);
-    uint32_t a = kp_entry(lane, ps, C, known, e, first, __shfl_up(sexit, 1, kWave));
-    uint32_t x = kz_verify<C>(w, ps, lane, nb, bm[lane], sexit, a);
-    bool settled = true;
-    for (int round = 0;; round++) {
-        const uint32_t px = __shfl_up(x, 1, kWave);
-        const uint64_t wrong = wballot(lane > 0 && a != px);
-        if (wrong == 0) break;
-        if (round >= kZFixRounds) {
-            settled = false;
-            break;
-        }
-        const int jf = ffs64(wrong);
-        kz_fix<C>(w, ps, lane, nb, bm[lane], sexit, jf, (uint32_t)__shfl((int)x, jf - 1, kWave), a, x);
-    }
+    const KzWalk k = kz_walk<C>(stage, bm, b, nb, sbase, ps, known, e);
     KpRec rec{0, kPNoEntry, 0, 0, 0};
-    if (!settled) return rec;
-    const KzSum r = kz_sum<C>(w, ps, lane, nb, a, x, lim32, limit);
-    uint64_t io = r.out;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t v = __shfl_up(io, d, kWave);
-        if (lane >= d) io += v;
-    }
-    uint32_t md = r.maxd;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) md = max(md, (uint32_t)__shfl_xor((int)md, d, kWave));
+    if (!k.settled) return rec;
+    const KzSum r = kz_sum<C>(KzWin{stage, sbase}, ps, lane, nb, k.a, k.x, lim32, limit);
+    const uint64_t io = wscan_add_u64(r.out);
     // (kp_append over the lanes in order)
     const bool bad = wballot((r.fl & kZBad) != 0) != 0;
     const uint64_t rm = wballot((r.fl & kZReset) != 0);
     const bool late = wballot((r.fl & kZReset) && ((r.fl & kZResetLate) || io != r.out)) != 0;
     rec.out = __shfl(io, kWave - 1, kWave);
-    rec.ent = (uint32_t)__shfl((int)a, 0, kWave);
-    rec.exit = (uint32_t)__shfl((int)x, kWave - 1, kWave);
-    rec.maxd = md;
+    rec.ent = (uint32_t)__shfl((int)k.a, 0, kWave);
+    rec.exit = (uint32_t)__shfl((int)k.x, kWave - 1, kWave);
+    rec.maxd = wmax_u32(r.maxd);
     rec.fl = bad ? kZBad : 0u;
     if (rm) rec.fl |= kZReset | (late ? kZResetLate : 0u) | ((uint32_t)__shfl((int)r.fl, 63 - __builtin_clzll(rm), kWave) & 0xff00u);
     return rec;
@@ -144,7 +107,7 @@ __global__ __launch_bounds__(64) void kp_first(DecompressArgs A, uint32_t *hdr, 
     if (hdr[kHGate] == 0) return;
     const uint32_t parts = hdr[kHParts];
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     uint32_t done = 0;
     for (uint32_t g = blockIdx.x; g < parts; g += gridDim.x) {
         const uint64_t s = kp_stream_of(base, A.count, g);
@@ -164,7 +127,7 @@ __global__ __launch_bounds__(64) void kp_order(DecompressArgs A, uint32_t *hdr, 
     if (hdr[kHGate] == 0) return;
     const int lane = lane_id();
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     uint32_t joined = 0, walked = 0;
     for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
         const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
@@ -206,8 +169,7 @@ __global__ __launch_bounds__(64) void kp_order(DecompressArgs A, uint32_t *hdr, 
         const bool ok = kp_end_ok(S, nb);
         if (lane == 0) {
             if (!ok) {
-                const uint32_t at = atomicAdd(&A.slow[0], 1u);
-                A.slow[1 + at] = (uint32_t)s;
+                slow_append(A, s);
             } else {
                 A.out_size[s] = S.total;
                 if (A.status) A.status[s] = EZ_OK;

@@ -118,7 +118,7 @@ __host__ __device__ __forceinline__ bool ring_one(const DecompressArgs &A, const
     uint8_t *out = A.out + A.out_off[s];
     const int64_t cap64 = (int64_t)(A.out_off[s + 1] - A.out_off[s]);
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;  // 0: no limit
+    const int32_t lim32 = k2_lim32(limit);  // 0: no limit
     // 32-bit positions; clamped loads need >= 16 input bytes in the batch and a 16-byte slot
     bool slow = in_end - A.in < 16 || nb64 >= (1ll << 30) || cap64 >= (1ll << 30) || cap64 < 16;
     const int32_t nb = slow ? 0 : (int32_t)nb64, cap = (int32_t)cap64;
@@ -369,8 +369,7 @@ __global__ __launch_bounds__(kRingBlock) void k2_ring(DecompressArgs A, uint32_t
     const uint64_t per_block = (uint64_t)(kRingBlock / 64) * spw;
     for (uint64_t s = (uint64_t)blockIdx.x * per_block + w * spw + l; s < A.count; s += (uint64_t)gridDim.x * per_block)
         if (!ring_one<HW>(A, s, ring, fper)) {
-            const uint32_t at = atomicAdd(&A.slow[0], 1u);
-            A.slow[1 + at] = (uint32_t)s;
+            slow_append(A, s);
         }
 }
 

@@ -6,8 +6,8 @@
 // output is k + 1 streams that decode on their own, and every fast decoder hands such a stream over
 // whole.  K2g finds the cuts on the device, so that the decoders get one stream per segment.  The
 // walk is K2z's (ez_decompress_size.hip: one wave per stream, grid-stride, super-blocks of 64 chunks
-// staged in LDS, a chunk per lane, kz_spec / kz_verify / kz_fix unchanged); in place of kz_sum, the
-// steps of ez_k2_segs.h:
+// staged in LDS, a chunk per lane, settled by kz_walk, ez_k2_walk.h); in place of kz_sum, the steps of
+// ez_k2_segs.h:
 //   sum      kg_sum over each lane's true chain up to the chunk's first event (a MetaReset, a form
 //            k2_scan hands over);
 //   reduce   an in-order prefix over the lanes for the output bytes; a super-block without an event
@@ -33,20 +33,12 @@
 #include "ez_cache.h"
 #include "ez_internal.h"
 #include "ez_k2_segs.h"
-#include "ez_wave.h"
+#include "ez_k2_walk.h"
 
 namespace ez {
 namespace {
 
 constexpr uint32_t kGKeep = 15;  // cuts the count pass keeps per stream (streams of up to 16 segments are walked once)
-
-// the longest distance of the lanes lo .. hi
-__device__ __forceinline__ uint32_t wmax_lanes(uint32_t v, int lane, int lo, int hi) {
-    v = lane >= lo && lane <= hi ? v : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, kWave));
-    return v;
-}
 
 template <int C, bool FILL>
 __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
@@ -56,7 +48,7 @@ __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
     if (FILL && A.hdr[0]) return;            // (the one-segment-per-stream layout: no cuts to write)
     const int lane = lane_id();
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
         uint64_t g0 = 0, nseg = 0;
         if (FILL) {
@@ -83,43 +75,14 @@ __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
         KgState st = kg_start();
         uint32_t sb = 0;
         while (!st.stop && sb < nb) {
-            __syncthreads();  // (the previous super-block's reads are done)
-            const uint32_t need = nb - sb + 16 < kz_stage_bytes(C) ? nb - sb + 16 : kz_stage_bytes(C);
-            for (uint32_t o = (uint32_t)lane * 16; o < need; o += kWave * 16) {
-                const uint32_t y = sb + o;
-                V16 v{0, 0};
-                if (y + 16 <= nb) v = ld16v(b + y);
-                else if (y < nb) v = ld_clamped(b + y, b, b + nb);
-                typedef uint64_t __attribute__((aligned(8))) u64a;
-                *(u64a *)(stage + o) = v.lo;
-                *(u64a *)(stage + o + 8) = v.hi;
+            const KzWalk k = kz_walk<C>(stage, bm, b, nb, sb, sb, true, sb);
+            if (!k.settled) {
+                st.stop = true;
+                break;
             }
-            __syncthreads();
             const KzWin w{stage, sb};
-            const uint32_t sexit = kz_spec<C>(w, sb, lane, nb, bm[lane]);
-            // lane k's entry is lane k-1's exit; lane 0 walked the true chain from sb
-            uint32_t a = __shfl_up(sexit, 1, kWave);
-            if (lane == 0) a = sb;
-            uint32_t x = lane == 0 ? sexit : kz_verify<C>(w, sb, lane, nb, bm[lane], sexit, a);
-            for (int round = 0;; round++) {
-                const uint32_t px = __shfl_up(x, 1, kWave);
-                const uint64_t wrong = wballot(lane > 0 && a != px);
-                if (wrong == 0) break;
-                if (round >= kZFixRounds) {
-                    st.stop = true;
-                    break;
-                }
-                const int jf = ffs64(wrong);
-                kz_fix<C>(w, sb, lane, nb, bm[lane], sexit, jf, (uint32_t)__shfl((int)x, jf - 1, kWave), a, x);
-            }
-            if (st.stop) break;
-            const KgSum r = kg_sum<C>(w, sb, lane, nb, a, x, lim32, limit);
-            uint64_t io = r.out;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const uint64_t v = __shfl_up(io, d, kWave);
-                if (lane >= d) io += v;
-            }
+            const KgSum r = kg_sum<C>(w, sb, lane, nb, k.a, k.x, lim32, limit);
+            const uint64_t io = wscan_add_u64(r.out);
             uint64_t ev = wballot(r.fl != 0);
             uint64_t base = 0;  // the prefix taken into the state so far
             int from = 0;       // the first lane whose distances are not in the state yet
@@ -130,15 +93,15 @@ __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
                 const uint64_t ioj = __shfl(io, j, kWave);
                 st.total += ioj - base;
                 base = ioj;
-                st.maxd = max(st.maxd, wmax_lanes(r.maxd, lane, from, j));
+                st.maxd = max(st.maxd, wmax_u32(lane >= from && lane <= j ? r.maxd : 0u));
                 from = j + 1;
-                kg_cuts<C>(w, sb, j, nb, (uint32_t)__shfl((int)r.epos, j, kWave), (uint32_t)__shfl((int)x, j, kWave), lim32, limit, st, cut);
+                kg_cuts<C>(w, sb, j, nb, (uint32_t)__shfl((int)r.epos, j, kWave), (uint32_t)__shfl((int)k.x, j, kWave), lim32, limit, st, cut);
                 if (st.stop) break;
             }
             if (st.stop) break;
             st.total += __shfl(io, kWave - 1, kWave) - base;
-            st.maxd = max(st.maxd, wmax_lanes(r.maxd, lane, from, kWave - 1));
-            sb = __shfl(x, kWave - 1, kWave);
+            st.maxd = max(st.maxd, wmax_u32(lane >= from ? r.maxd : 0u));
+            sb = __shfl(k.x, kWave - 1, kWave);
         }
         if (!FILL && lane == 0) A.seg_idx[s] = (uint64_t)st.ncut + 1;
     }

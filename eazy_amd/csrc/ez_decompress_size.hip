@@ -3,17 +3,12 @@
 // A decoded length depends on the tokens alone (Reader.read reader.go:143-216 adds every token's
 // length, whatever its bytes are), so the query reads token headers, skips every literal's body and
 // writes one u64 per stream.  One wave per stream, grid-stride over the streams.  The token chain is
-// cut inside the wave by speculation (the steps: ez_k2_size.h): the stream is taken in super-blocks
-// of 64 chunks of C input bytes, a chunk per lane.  Per super-block, which starts at the true chain's
-// position sb:
-//   stage    the super-block's 64 x C bytes and the 16 a header at its end reads go to LDS with
-//            16-byte loads, clamped to the stream (zeros past its end); every later step reads LDS;
-//   spec     kz_spec, a lane per chunk;
-//   verify   kz_verify from the predecessor's speculative exit; then, while a lane's assumed entry
-//            differs from its predecessor's verified exit, the lowest such lane re-walks (kz_fix; the
-//            lanes a spanning token covers take its end in the same round; at most 63 rounds,
-//            bounded by a counter that hands the stream over);
-//   sum      kz_sum over each lane's true chain;
+// cut inside the wave by speculation: the stream is taken in super-blocks of 64 chunks of C input
+// bytes, a chunk per lane.  Per super-block, which starts at the true chain's position sb:
+//   walk     kz_walk (ez_k2_walk.h): the super-block's 64 x C bytes and the 16 a header at its end reads
+//            are staged in LDS, and the wave settles every lane's entry and exit on the true chain (a
+//            super-block that does not settle within the bound hands the stream over);
+//   sum      kz_sum (ez_k2_size.h) over each lane's true chain;
 //   reduce   an in-order prefix over the lanes for the output bytes and the reset-before-any-output
 //            rule; the totals, the window and the flags are carried.
 // The next super-block starts at lane 63's true exit: a literal's body is never staged or read, however
@@ -24,8 +19,7 @@
 
 #include "ez_bytes.h"
 #include "ez_internal.h"
-#include "ez_k2_size.h"
-#include "ez_wave.h"
+#include "ez_k2_walk.h"
 
 namespace ez {
 namespace {
@@ -38,7 +32,7 @@ __global__ __launch_bounds__(64) void k2z_size(DecompressArgs A) {
     const bool parted = A.size_gate && *A.size_gate;  // (the parts route sized the streams that have parts)
     const int lane = lane_id();
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
         if (parted && A.size_base[s] != A.size_base[s + 1]) continue;
         const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
@@ -49,58 +43,24 @@ __global__ __launch_bounds__(64) void k2z_size(DecompressArgs A) {
         uint64_t total = 0;
         int32_t bsl = -1;
         while (!bad && sb < nb) {
-            __syncthreads();  // (the previous super-block's reads are done)
-            const uint32_t need = nb - sb + 16 < kz_stage_bytes(C) ? nb - sb + 16 : kz_stage_bytes(C);
-            for (uint32_t o = (uint32_t)lane * 16; o < need; o += kWave * 16) {
-                const uint32_t y = sb + o;
-                V16 v{0, 0};
-                if (y + 16 <= nb) v = ld16v(b + y);
-                else if (y < nb) v = ld_clamped(b + y, b, b + nb);
-                typedef uint64_t __attribute__((aligned(8))) u64a;
-                *(u64a *)(stage + o) = v.lo;
-                *(u64a *)(stage + o + 8) = v.hi;
+            const KzWalk k = kz_walk<C>(stage, bm, b, nb, sb, sb, true, sb);
+            if (!k.settled) {
+                bad = true;
+                break;
             }
-            __syncthreads();
-            const KzWin w{stage, sb};
-            const uint32_t sexit = kz_spec<C>(w, sb, lane, nb, bm[lane]);
-            // lane k's entry is lane k-1's exit; lane 0 walked the true chain from sb
-            uint32_t a = __shfl_up(sexit, 1, kWave);
-            if (lane == 0) a = sb;
-            uint32_t x = lane == 0 ? sexit : kz_verify<C>(w, sb, lane, nb, bm[lane], sexit, a);
-            for (int round = 0;; round++) {
-                const uint32_t px = __shfl_up(x, 1, kWave);
-                const uint64_t wrong = wballot(lane > 0 && a != px);
-                if (wrong == 0) break;
-                if (round >= kZFixRounds) {
-                    bad = true;
-                    break;
-                }
-                const int jf = ffs64(wrong);
-                kz_fix<C>(w, sb, lane, nb, bm[lane], sexit, jf, (uint32_t)__shfl((int)x, jf - 1, kWave), a, x);
-            }
-            if (bad) break;
-            const KzSum r = kz_sum<C>(w, sb, lane, nb, a, x, lim32, limit);
-            uint64_t io = r.out;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const uint64_t v = __shfl_up(io, d, kWave);
-                if (lane >= d) io += v;
-            }
-            uint32_t md = r.maxd;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) md = max(md, (uint32_t)__shfl_xor((int)md, d, kWave));
-            maxd = max(maxd, md);
+            const KzSum r = kz_sum<C>(KzWin{stage, sb}, sb, lane, nb, k.a, k.x, lim32, limit);
+            const uint64_t io = wscan_add_u64(r.out);
+            maxd = max(maxd, wmax_u32(r.maxd));
             if (wballot((r.fl & kZBad) || kz_reset_bad(r.fl, total + io - r.out))) bad = true;
             const uint64_t rm = wballot((r.fl & kZReset) != 0);
             if (rm) bsl = (int32_t)((__shfl((int)r.fl, 63 - __builtin_clzll(rm), kWave) >> 8) & 0xff);
             total += __shfl(io, kWave - 1, kWave);
-            sb = __shfl(x, kWave - 1, kWave);
+            sb = __shfl(k.x, kWave - 1, kWave);
         }
         if (!bad) bad = !kz_end_ok(sb, nb, total, bsl, maxd);
         if (lane == 0) {
             if (bad) {
-                const uint32_t at = atomicAdd(&A.slow[0], 1u);
-                A.slow[1 + at] = (uint32_t)s;
+                slow_append(A, s);
             } else {
                 A.out_size[s] = total;
                 if (A.status) A.status[s] = EZ_OK;
@@ -117,7 +77,7 @@ __global__ __launch_bounds__(64) void k2z_size(DecompressArgs A) {
 __global__ __launch_bounds__(64) void k2z_lane(DecompressArgs A) {
     const bool parted = A.size_gate && *A.size_gate;  // (the parts route sized the streams that have parts)
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     for (uint64_t s = (uint64_t)blockIdx.x * kWave + threadIdx.x; s < A.count; s += (uint64_t)gridDim.x * kWave) {
         if (parted && A.size_base[s] != A.size_base[s + 1]) continue;
         const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
@@ -126,14 +86,13 @@ __global__ __launch_bounds__(64) void k2z_lane(DecompressArgs A) {
         bool ok = nb64 < (1ull << 31);
         if (ok) {
             const uint32_t nb = (uint32_t)nb64;
-            ok = kz_serial([=](uint32_t p) { return p + 16 <= nb ? ld16v(b + p) : ld_clamped(b + p, b, b + nb); }, nb, lim32, limit, total);
+            ok = kz_serial(kz_global_at(b, nb), nb, lim32, limit, total);
         }
         if (ok) {
             A.out_size[s] = total;
             if (A.status) A.status[s] = EZ_OK;
         } else {
-            const uint32_t at = atomicAdd(&A.slow[0], 1u);
-            A.slow[1 + at] = (uint32_t)s;
+            slow_append(A, s);
         }
     }
 }

@@ -47,7 +47,7 @@ __device__ bool wave_one(const DecompressArgs &A, const uint64_t s, uint8_t *rin
     uint8_t *out = A.out + A.out_off[s];
     const int64_t cap64 = (int64_t)(A.out_off[s + 1] - A.out_off[s]);
     const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     if (in_end - A.in < 16 || nb64 >= (1ll << 30) || cap64 >= (1ll << 30) || cap64 < 16) return false;
     const int32_t nb = (int32_t)nb64, cap = (int32_t)cap64;
     // zero ring = the fresh window's zero history
@@ -297,8 +297,7 @@ __global__ __launch_bounds__(64) void k2_wave(DecompressArgs A) {
     const int lane = (int)threadIdx.x;
     for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x)
         if (!wave_one(A, s, ring, inb, defs, lane) && lane == 0) {
-            const uint32_t at = atomicAdd(&A.slow[0], 1u);
-            A.slow[1 + at] = (uint32_t)s;
+            slow_append(A, s);
         }
 }
 

@@ -154,6 +154,12 @@ struct DecompressArgs {
     const uint32_t *size_base;
 };
 
+// a fast path hands stream s over: appended to the slow list (one lane per stream calls this)
+__device__ __forceinline__ void slow_append(const DecompressArgs &A, uint64_t s) {
+    const uint32_t at = atomicAdd(&A.slow[0], 1u);
+    A.slow[1 + at] = (uint32_t)s;
+}
+
 // words of workspace the two-level batch decoder needs
 uint64_t decompress_workspace_words(uint64_t count);
 

@@ -34,6 +34,11 @@ enum { kScanReset = 2 };  // k2_scan only: a MetaReset, valid only before any ou
 // header is whole and whose body runs past the end (read copies the bytes there are, :166-168)
 enum { kScanTail = 3 };
 
+// BlockSizeLimit clamped to 32 bits for k2_scan (0: no limit)
+__host__ __device__ __forceinline__ int32_t k2_lim32(int64_t limit) {
+    return limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+}
+
 // The checks that do not depend on the decoder's state, for a step at input position
 // i: returns kParseSkip (padding, break, version, magic), kScanReset, kParseToken or
 // kParseHandOver.  h = input bytes i .. i+15 (zeros past the batch); nb = stream

@@ -5,9 +5,9 @@
 // [k * 64 * C, (k + 1) * 64 * C)); a stream without parts (an empty one, one of 2 GiB or more, one the
 // automatic route's probe leaves to the wave route) is sized by the wave route.  The first pass gives every part a wave, which cannot know where
 // the true chain enters its part: lane 0 warms up over the chunk before the part as the other lanes
-// do over the chunk before theirs (kp_spec), and the part's chain is the one that follows from lane
-// 0's first position in the part (verify, repair and sum are ez_k2_size.h's, a part standing for a
-// super-block).  The part's record (KpRec) holds that assumed entry, the chain's exit and its sums.
+// do over the chunk before theirs (kz_spec without a known entry), and the part's chain is the one
+// that follows from lane 0's first position in the part (the walk is kz_walk, ez_k2_walk.h, and the sum
+// ez_k2_size.h's).  The part's record (KpRec) holds that assumed entry, the chain's exit and its sums.
 // The in-order pass, a wave per stream, then follows the true chain from part to part (kp_take): a
 // part the chain enters at or past its end is passed through (a token spans it), a part whose record
 // starts at the true entry is taken as recorded, and any other part is walked again from the true
@@ -69,41 +69,6 @@ struct KpRec {
     uint32_t maxd;  // its longest copy distance
     uint32_t fl;    // KzSum.fl of the whole part (kZResetLate: output in this part before a MetaReset)
 };
-
-// The speculative walk of lane's chunk of the part at ps.  known: e is the true chain's position, at
-// or past ps: the lane whose chunk holds e starts there (no warm-up: it is on the true chain as lane 0
-// of a super-block is), the lanes before it visit nothing.  Every other lane warms up over the chunk
-// before its own, lane 0 over the staged chunk before the part (from 0 in the stream's first part,
-// which is the true entry).  bm: the positions visited in the chunk; first: the first of them (the
-// walk's exit if none); returns where the walk leaves the chunk.
-template <int C>
-EZ_HD uint32_t kp_spec(const KzWin &w, uint32_t ps, int lane, uint32_t nb, bool known, uint32_t e, uint32_t *bm, uint32_t &first) {
-    uint32_t c0, ce;
-    kz_chunk<C>(ps, lane, nb, c0, ce);
-    for (int k = 0; k < C / 32; k++) bm[k] = 0;
-    first = c0;
-    if (c0 >= nb) return c0;
-    if (known && e >= ce) {  // (the true chain enters after this chunk)
-        first = e;
-        return e;
-    }
-    uint32_t p = known && e >= c0 ? e : (c0 >= (uint32_t)C ? c0 - (uint32_t)C : 0u);
-    while (p < c0) p = kz_next(w, p, nb);
-    first = p;
-    while (p < ce) {
-        bm[(p - c0) >> 5] |= 1u << ((p - c0) & 31);
-        p = kz_next(w, p, nb);
-    }
-    return p;
-}
-
-// lane's assumed entry after kp_spec: the predecessor's speculative exit; lane 0 (and, with a known
-// entry e, every lane up to the one that holds e) its own first position
-EZ_HD uint32_t kp_entry(int lane, uint32_t ps, uint32_t c, bool known, uint32_t e, uint32_t first, uint32_t prev_exit) {
-    if (lane == 0) return known ? e : first;
-    if (known && e >= ps + (uint32_t)lane * c) return e;  // (the chunks before the holder's, and the holder's)
-    return prev_exit;
-}
 
 // b after a in the chain's order (a: what precedes, sums of a part or of the stream so far)
 EZ_HD void kp_append(KzSum &a, const KzSum &b) {

@@ -4,7 +4,7 @@
 // Reader.reset (reader.go:327-344) zeroes the block and sets r.pos = 0, so everything from a MetaReset
 // on decodes exactly like a fresh stream: a stream with k Resets after output is k + 1 streams whose
 // input and output ranges tile its own.  The cuts lie on the true token chain (a literal's body may
-// hold 80 10 14), which K2g follows as K2z does (ez_k2_size.h: kz_spec, kz_verify, kz_fix, unchanged).
+// hold 80 10 14), which K2g follows as K2z does (kz_walk, ez_k2_walk.h, over ez_k2_size.h's steps).
 // In place of kz_sum:
 //   kg_sum     a lane walks its chunk's true chain with the full k2_scan up to the chunk's first event,
 //              a MetaReset or a form k2_scan hands over, and records the event's input position (a

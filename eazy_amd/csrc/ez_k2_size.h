@@ -1,22 +1,25 @@
 // ez_k2_size.h — the per-lane steps of K2z, the batch decoded-size query (ez_decompress_size.hip):
 // a stream's output length from its token headers alone.
 //
-// A wave takes a stream in super-blocks of 64 chunks of C input bytes, a chunk per lane, staged so
-// that every step reads the staged bytes only.  The token chain (every token starts where the
-// previous one ends, readTag reader.go:218-270) is cut as K2j cuts it (ez_decompress_jump.hip):
+// A wave takes a stream in blocks of 64 chunks of C input bytes, a chunk per lane, staged so that
+// every step reads the staged bytes only: a super-block, which starts at the true chain's position
+// (K2z's wave route, K2g), or a part on a fixed grid (K2z's parts route, ez_k2_parts.h).  The token
+// chain (every token starts where the previous one ends, readTag reader.go:218-270) is cut as K2j
+// cuts it (ez_decompress_jump.hip); kz_walk (ez_k2_walk.h) drives the first four steps over the wave:
 //   kz_spec    a lane parses speculatively from up to one chunk before its own and records the
 //              positions it visits inside its chunk (a bitmap) and where it leaves it;
-//   kz_verify  from the predecessor's exit it walks until it meets a recorded position (its exit is
-//              then the speculative one) or leaves the chunk; an entry at or past the chunk's end (a
-//              token that spans the chunk) passes through;
+//   kz_entry   its assumed entry: the predecessor's speculative exit, or the true position;
+//   kz_verify  from its entry it walks until it meets a recorded position (its exit is then the
+//              speculative one) or leaves the chunk; an entry at or past the chunk's end (a token that
+//              spans the chunk) passes through;
 //   kz_fix     one round of the repair where a lane's assumed entry was not its predecessor's exit;
 //   kz_sum     it walks its true chain once with the full k2_scan (ez_k2_parse.h) and sums the output
 //              bytes, the longest distance and the flags the stream's checks need;
 //   kz_end_ok  the checks at the stream's end (kj_scan's, without a slot).
-// All of them are functions over a byte pointer, so tools/k2_size_check.hip runs the same source on
-// the host over 64 emulated lanes.  Positions are stream offsets in uint32_t: a stream is shorter
-// than 2^31 bytes (longer ones are handed over before any step) and a step takes less than 2^31, so
-// no sum wraps.
+// All of them are functions over a byte pointer, so the host checks run the same source over 64
+// emulated lanes (tools/k2_check_common.h: emu_walk, the mirror of kz_walk).  Positions are stream
+// offsets in uint32_t: a stream is shorter than 2^31 bytes (longer ones are handed over before any
+// step) and a step takes less than 2^31, so no sum wraps.
 #pragma once
 
 #include "ez_k2_parse.h"
@@ -58,23 +61,41 @@ EZ_HD void kz_chunk(uint32_t sb, int lane, uint32_t nb, uint32_t &c0, uint32_t &
     ce = c0 + C < nb ? c0 + C : nb;
 }
 
-// The speculative walk: bm[0 .. C/32) gets the positions visited in the chunk, the return value is
-// where the walk leaves it.  Lane 0 starts at sb, the true chain's position; the others warm up over
-// the chunk before theirs (inside the staged bytes), so that their chain has usually met the true
-// one by their chunk's start.
+// The speculative walk of lane's chunk of the block at ps.  known: e is the true chain's position, at
+// or past ps: the lane whose chunk holds e starts there (no warm-up: it is on the true chain), the
+// lanes before it visit nothing.  A super-block starts at the true position: known, e = ps, and lane 0
+// holds it.  Every other lane warms up over the chunk before its own (inside the staged bytes), so
+// that its chain has usually met the true one by its chunk's start; lane 0 of a part over the staged
+// chunk before the part (from 0 in the stream's first part, which is the true entry).  bm[0 .. C/32):
+// the positions visited in the chunk; first: the first of them (the walk's exit if none); returns
+// where the walk leaves the chunk.
 template <int C>
-EZ_HD uint32_t kz_spec(const KzWin &w, uint32_t sb, int lane, uint32_t nb, uint32_t *bm) {
+EZ_HD uint32_t kz_spec(const KzWin &w, uint32_t ps, int lane, uint32_t nb, bool known, uint32_t e, uint32_t *bm, uint32_t &first) {
     uint32_t c0, ce;
-    kz_chunk<C>(sb, lane, nb, c0, ce);
+    kz_chunk<C>(ps, lane, nb, c0, ce);
     for (int k = 0; k < C / 32; k++) bm[k] = 0;
+    first = c0;
     if (c0 >= nb) return c0;
-    uint32_t p = lane == 0 ? sb : c0 - C;
+    if (known && e >= ce) {  // (the true chain enters after this chunk)
+        first = e;
+        return e;
+    }
+    uint32_t p = known && e >= c0 ? e : (c0 >= (uint32_t)C ? c0 - (uint32_t)C : 0u);
     while (p < c0) p = kz_next(w, p, nb);
+    first = p;
     while (p < ce) {
         bm[(p - c0) >> 5] |= 1u << ((p - c0) & 31);
         p = kz_next(w, p, nb);
     }
     return p;
+}
+
+// lane's assumed entry after kz_spec: the predecessor's speculative exit; lane 0 (and, with a known
+// entry e, every lane up to the one that holds e) its own first position
+EZ_HD uint32_t kz_entry(int lane, uint32_t ps, uint32_t c, bool known, uint32_t e, uint32_t first, uint32_t prev_exit) {
+    if (lane == 0) return known ? e : first;
+    if (known && e >= ps + (uint32_t)lane * c) return e;  // (the chunks before the holder's, and the holder's)
+    return prev_exit;
 }
 
 // The chunk's exit for the entry a (a >= c0: a predecessor leaves at or past its own end): a walk from

@@ -36,6 +36,22 @@ __device__ __forceinline__ int32_t wshr1(int32_t v, int32_t first) {
     return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false);
 }
 
+// inclusive 64-bit prefix sum over the wave's lanes, in lane order
+__device__ __forceinline__ uint64_t wscan_add_u64(uint64_t v) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint64_t u = __shfl_up(v, d, kWave);
+        if (lane_id() >= d) v += u;
+    }
+    return v;
+}
+// the maximum over the wave's lanes, in every lane
+__device__ __forceinline__ uint32_t wmax_u32(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, kWave));
+    return v;
+}
+
 // first set lane of a ballot mask (mask != 0)
 __device__ __forceinline__ int ffs64(uint64_t m) { return (int)__builtin_ctzll(m); }
 

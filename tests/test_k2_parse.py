@@ -5,14 +5,14 @@ first three bytes, edge values in the next five, zero runs, the metas, and the i
 point inside a header.  CPU only; the program exits non-zero at its first mismatch and prints the
 header."""
 
-import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK = os.path.join(ROOT, "tools", "k2_parse_check")
+import k2_check_build
+
+HEADERS = k2_check_build.COMMON
 
 # the classes the program counts: each must have been visited
 CLASSES = ("headers", "pad", "skip", "reset", "lit", "copy", "zero_region", "rejected", "handed_wide_meta", "handed_big", "fast",
@@ -22,20 +22,7 @@ CLASSES = ("headers", "pad", "skip", "reset", "lit", "copy", "zero_region", "rej
 
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
-    src = os.path.join(ROOT, "tools", "k2_parse_check.hip")
-    orc_c = os.path.join(ROOT, "oracle", "eazy_oracle.c")
-    deps = [src, orc_c, os.path.join(ROOT, "oracle", "eazy_oracle.h"), os.path.join(ROOT, "include", "eazy.h")]
-    deps += [os.path.join(ROOT, "eazy_amd", "csrc", f) for f in ("ez_k2_parse.h", "ez_bytes.h", "ez_format.h")]
-    if not os.path.exists(CHECK) or os.path.getmtime(CHECK) < max(os.path.getmtime(d) for d in deps):
-        tmp = tmp_path_factory.mktemp("k2_parse")
-        orc_o, chk_o = str(tmp / "eazy_oracle.o"), str(tmp / "k2_parse_check.o")
-        hipcc = "/opt/rocm/bin/hipcc"
-        for cmd in (["gcc", "-O2", "-std=c11", "-c", "-o", orc_o, orc_c],
-                    [hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "-Wno-align-mismatch", "-c", "-o", chk_o, src],
-                    [hipcc, "-o", CHECK, chk_o, orc_o, "-lpthread"]):
-            p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-            assert p.returncode == 0, p.stderr[-2000:]
-    return CHECK
+    return k2_check_build.build_check("k2_parse_check", tmp_path_factory.mktemp("k2_parse"), HEADERS)
 
 
 def test_parse_primitives_match_oracle(check):

@@ -13,14 +13,14 @@ single lane's walk of the whole chain, the number of cuts is the one the stream 
 each segment decoded alone by the oracle's Reader, joined, is the whole stream's output and error.
 CPU only; the program exits non-zero at its first mismatch and prints the stream."""
 
-import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK = os.path.join(ROOT, "tools", "k2_segs_check")
+import k2_check_build
+
+HEADERS = k2_check_build.COMMON + k2_check_build.csrc("ez_k2_segs.h", "ez_k2_walk.h")  # (ez_k2_walk.h: what emu_walk mirrors)
 
 # the classes the program counts: each must have been visited
 CLASSES = ("streams", "cuts_found", "with_cuts", "stops", "stops_with_cuts", "seam_chunk", "seam_super", "packed", "packed_chunk",
@@ -31,19 +31,7 @@ CLASSES = ("streams", "cuts_found", "with_cuts", "stops", "stops_with_cuts", "se
 
 def build_check(tmp):
     """tools/k2_segs_check, built when it is missing or older than its sources."""
-    src = os.path.join(ROOT, "tools", "k2_segs_check.hip")
-    orc_c = os.path.join(ROOT, "oracle", "eazy_oracle.c")
-    deps = [src, orc_c, os.path.join(ROOT, "oracle", "eazy_oracle.h"), os.path.join(ROOT, "include", "eazy.h")]
-    deps += [os.path.join(ROOT, "eazy_amd", "csrc", f) for f in ("ez_k2_segs.h", "ez_k2_size.h", "ez_k2_parse.h", "ez_bytes.h", "ez_format.h")]
-    if not os.path.exists(CHECK) or os.path.getmtime(CHECK) < max(os.path.getmtime(d) for d in deps):
-        orc_o, chk_o = str(tmp / "eazy_oracle.o"), str(tmp / "k2_segs_check.o")
-        hipcc = "/opt/rocm/bin/hipcc"
-        for cmd in (["gcc", "-O2", "-std=c11", "-c", "-o", orc_o, orc_c],
-                    [hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "-Wno-align-mismatch", "-c", "-o", chk_o, src],
-                    [hipcc, "-o", CHECK, chk_o, orc_o, "-lpthread"]):
-            p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-            assert p.returncode == 0, p.stderr[-2000:]
-    return CHECK
+    return k2_check_build.build_check("k2_segs_check", tmp, HEADERS)
 
 
 @pytest.fixture(scope="module")

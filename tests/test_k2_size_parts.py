@@ -14,14 +14,14 @@ walk of the whole chain.  CPU only; the program exits non-zero at its first mism
 Also here: the route's C entry points are exported and refuse bad arguments without a device."""
 
 import ctypes
-import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECK = os.path.join(ROOT, "tools", "k2_size_parts_check")
+import k2_check_build
+
+HEADERS = k2_check_build.COMMON + k2_check_build.csrc("ez_k2_walk.h")  # (ez_k2_walk.h: what emu_walk mirrors)
 
 # the classes the program counts: each must have been visited
 CLASSES = ("streams", "taken", "handed_error", "handed_design", "seam_part", "lit_within", "lit_one_part", "lit_many_parts", "adversarial",
@@ -31,20 +31,7 @@ CLASSES = ("streams", "taken", "handed_error", "handed_design", "seam_part", "li
 
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
-    src = os.path.join(ROOT, "tools", "k2_size_parts_check.hip")
-    orc_c = os.path.join(ROOT, "oracle", "eazy_oracle.c")
-    deps = [src, orc_c, os.path.join(ROOT, "oracle", "eazy_oracle.h"), os.path.join(ROOT, "include", "eazy.h")]
-    deps += [os.path.join(ROOT, "eazy_amd", "csrc", f) for f in ("ez_k2_parts.h", "ez_k2_size.h", "ez_k2_parse.h", "ez_bytes.h", "ez_format.h")]
-    if not os.path.exists(CHECK) or os.path.getmtime(CHECK) < max(os.path.getmtime(d) for d in deps):
-        tmp = tmp_path_factory.mktemp("k2_size_parts")
-        orc_o, chk_o = str(tmp / "eazy_oracle.o"), str(tmp / "k2_size_parts_check.o")
-        hipcc = "/opt/rocm/bin/hipcc"
-        for cmd in (["gcc", "-O2", "-std=c11", "-c", "-o", orc_o, orc_c],
-                    [hipcc, "-O2", "-std=c++17", "--offload-arch=gfx950", "-Wno-align-mismatch", "-c", "-o", chk_o, src],
-                    [hipcc, "-o", CHECK, chk_o, orc_o, "-lpthread"]):
-            p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-            assert p.returncode == 0, p.stderr[-2000:]
-    return CHECK
+    return k2_check_build.build_check("k2_size_parts_check", tmp_path_factory.mktemp("k2_size_parts"), HEADERS, opt="-O2")
 
 
 def test_parts_steps_match_oracle(check):

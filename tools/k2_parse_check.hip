@@ -17,12 +17,10 @@
 //             for every form the Reader accepts; a literal whose header is whole and whose body is
 //             not: kScanTail with its j and L.  (A form the Reader rejects may stop at a tail or be
 //             handed over: the host Reader resumes at that token and reports its error.)
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+// (of the common header this check uses rnd() and the count printer only)
+#include "k2_check_common.h"
 
-#include "../eazy_amd/csrc/ez_k2_parse.h"
-#include "../oracle/eazy_oracle.h"
+using k2check::rnd;
 
 namespace {
 
@@ -251,13 +249,6 @@ void check_partial(const uint8_t *h) {
     }
 }
 
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-uint64_t rnd() {  // xorshift64*, fixed seed
-    g_rng ^= g_rng >> 12;
-    g_rng ^= g_rng << 25;
-    g_rng ^= g_rng >> 27;
-    return g_rng * 0x2545f4914f6cdd1dull;
-}
 void fill(uint8_t *h, int from) {
     const uint64_t a = rnd(), b = rnd();
     for (int k = from; k < 16; k++) h[k] = (uint8_t)((k < 8 ? a : b) >> (8 * (k & 7)));
@@ -326,7 +317,7 @@ int main() {
         meta(0x08 | 6, "\xfc\x01", 2);
         for (int ty = 4; ty < 32; ty++) meta((uint8_t)(ty << 3 | (k & 7)), "", 0);
     }
-#define P(f) std::printf("%-18s %llu\n", #f, (unsigned long long)C.f)
+#define P(f) K2_COUNT(C, 18, f)
     P(headers); P(pad); P(skip); P(reset); P(lit); P(copy); P(zero_region); P(rejected); P(handed_wide_meta); P(handed_big); P(fast);
     P(part_cuts); P(part_pad); P(part_token); P(tail_header); P(tail_literal); P(tail_rejected);
     P(m_break); P(m_reset_ok); P(m_reset_bad); P(m_ver_ok); P(m_ver_bad); P(m_magic_ok); P(m_magic_bad); P(m_wide); P(m_unknown);

@@ -1,6 +1,6 @@
 // Host check of K2g's per-lane steps (eazy_amd/csrc/ez_k2_segs.h, over ez_k2_size.h's walk): the same
 // source, compiled for the CPU and run over 64 emulated lanes as the kernel runs them
-// (ez_decompress_segs.hip: stage, speculate, verify and re-walk, kg_sum, then the events in lane order
+// (ez_decompress_segs.hip: the wave's walk of a super-block, kg_sum, then the events in lane order
 // through kg_cuts), for every chunk size.  Per stream:
 //   the cut list (input position, output position), the stop flag and, without a stop, the output
 //   total equal a single lane's walk of the whole chain (kg_serial);
@@ -11,22 +11,18 @@
 //   k2_segs_check             prints the count of every class, exits 1 at the first mismatch
 //   k2_segs_check --dump F    also writes every untruncated stream and its cuts to F (the GPU test's input)
 //
-// Streams (tokens written one by one with the oracle's Encoder): see main().  The staged bytes past
-// what the kernel stages are poisoned, and the buffers are exactly as long as the kernel's, so a
-// sanitizer build of this program shows a step reading outside them.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
+// Streams (tokens written one by one with the oracle's Encoder): see main().  The builder, the oracle
+// call and the wave's walk of a super-block (emu_walk, the mirror of kz_walk) are
+// tools/k2_check_common.h's; here are the events and cuts after it, the stream lists and the dump.
 #include <utility>
-#include <vector>
 
 #include "../eazy_amd/csrc/ez_k2_segs.h"
-#include "../oracle/eazy_oracle.h"
+#include "k2_check_common.h"
+
+using namespace k2check;
 
 namespace {
 
-typedef std::vector<uint8_t> Bytes;
 typedef std::vector<std::pair<uint32_t, uint64_t>> Cuts;
 
 struct Counts {
@@ -38,80 +34,13 @@ struct Counts {
 bool g_adversarial;  // the stream under check is one built to keep speculation off the true chain
 std::FILE *g_dump;
 
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-uint64_t rnd() {  // xorshift64*, fixed seed
-    g_rng ^= g_rng >> 12;
-    g_rng ^= g_rng << 25;
-    g_rng ^= g_rng >> 27;
-    return g_rng * 0x2545f4914f6cdd1dull;
-}
-
-// ---- the Encoder
-void put(Bytes &v, const uint8_t *p, size_t n) { v.insert(v.end(), p, p + n); }
-void put(Bytes &v, const Bytes &b) { v.insert(v.end(), b.begin(), b.end()); }
-void tag(Bytes &v, int tg, int64_t l) {
-    uint8_t t[32];
-    size_t n = 0;
-    if (or_enc_tag(t, &n, tg, l)) std::exit(2);
-    put(v, t, n);
-}
-void offset(Bytes &v, int64_t d, int64_t l) {
-    uint8_t t[32];
-    size_t n = 0;
-    if (or_enc_offset(t, &n, d, l)) std::exit(2);
-    put(v, t, n);
-}
-void lit_rnd(Bytes &v, int64_t n) {
-    tag(v, 0x00, n);
-    for (int64_t k = 0; k < n; k++) v.push_back((uint8_t)rnd());
-}
+// ---- the Encoder's forms of this check
 void lit_of(Bytes &v, const Bytes &body) {
     tag(v, 0x00, (int64_t)body.size());
     put(v, body);
 }
-void cpy(Bytes &v, int64_t d, int64_t n) {
-    tag(v, 0x80, n);
-    offset(v, d, n);
-}
-void meta(Bytes &v, int64_t m, const char *arg, int n) {
-    uint8_t t[32];
-    size_t k = 0;
-    if (or_enc_meta(t, &k, m, n)) std::exit(2);
-    put(v, t, k);
-    put(v, (const uint8_t *)arg, (size_t)n);
-}
-void magic(Bytes &v) { meta(v, 0 << 3, "eazy", 4); }
 void ver0(Bytes &v) { meta(v, 1 << 3, "\x00", 1); }
 void brk(Bytes &v) { meta(v, 3 << 3, "", 0); }
-void rst(Bytes &v, int bsl = 0x14) {  // 80 10 bsl
-    const char a = (char)bsl;
-    meta(v, 2 << 3, &a, 1);
-}
-void hdr(Bytes &v, int bsl = 0x14) {
-    magic(v);
-    rst(v, bsl);
-}
-
-// short literals and copies (distances up to maxd) up to exactly `target` bytes of stream
-void fill_to(Bytes &v, size_t target, int maxd = 200) {
-    while (v.size() < target) {
-        const size_t left = target - v.size();
-        if (left == 1) {
-            v.push_back(0);  // (one byte: padding)
-        } else if (left <= 100) {
-            lit_rnd(v, (int64_t)left - 1);
-        } else if (rnd() % 3 == 0) {
-            cpy(v, 1 + (int64_t)(rnd() % maxd), 4 + (int64_t)(rnd() % 60));
-        } else {
-            lit_rnd(v, 1 + (int64_t)(rnd() % 60));
-        }
-    }
-}
-void tail3(Bytes &v) {
-    lit_rnd(v, 5);
-    cpy(v, 3, 9);
-    lit_rnd(v, 2);
-}
 // a segment's tokens, about n bytes of stream
 void body(Bytes &v, size_t n, int maxd = 200) { fill_to(v, v.size() + n, maxd); }
 
@@ -125,8 +54,7 @@ struct Walk {
 template <int C>
 Walk emulate(const uint8_t *in, uint64_t nb64, int64_t limit) {
     using namespace ez;
-    constexpr int W = C / 32;
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const int32_t lim32 = k2_lim32(limit);
     const uint32_t nb = nb64 >= (1ull << 31) ? 0u : (uint32_t)nb64;
     Walk wk;
     auto cut = [&](uint32_t i, uint32_t pos, uint64_t out) {
@@ -138,50 +66,30 @@ Walk emulate(const uint8_t *in, uint64_t nb64, int64_t limit) {
     };
     KgState st = kg_start();
     uint32_t sb = 0;
-    // exactly the kernel's LDS: an access outside them is one outside the kernel's
-    uint8_t *stage = (uint8_t *)std::malloc(kz_stage_bytes(C));
-    uint32_t(*bm)[W] = (uint32_t(*)[W])std::malloc(sizeof(uint32_t) * W * kZLanes);
-    uint32_t sexit[kZLanes], a[kZLanes], x[kZLanes];
+    EmuWave<C> wv(kz_stage_bytes(C));
+    EmuStats es{};
     while (!st.stop && sb < nb) {
         N.superblocks++;
-        const uint32_t need = nb - sb + 16 < kz_stage_bytes(C) ? nb - sb + 16 : kz_stage_bytes(C);
-        std::memset(stage, 0xcc, kz_stage_bytes(C));  // (what the kernel leaves from earlier: never read)
-        for (uint32_t o = 0; o < need; o += 16)
-            for (uint32_t k = 0; k < 16; k++) stage[o + k] = sb + o + k < nb ? in[sb + o + k] : 0;
-        const KzWin w{stage, sb};
-        for (int l = 0; l < kZLanes; l++) sexit[l] = kz_spec<C>(w, sb, l, nb, bm[l]);
-        for (int l = 0; l < kZLanes; l++) a[l] = l == 0 ? sb : sexit[l - 1];
-        for (int l = 0; l < kZLanes; l++) x[l] = l == 0 ? sexit[0] : kz_verify<C>(w, sb, l, nb, bm[l], sexit[l], a[l]);
-        for (int round = 0;; round++) {
-            int jf = -1;
-            for (int l = 1; l < kZLanes && jf < 0; l++)
-                if (a[l] != x[l - 1]) jf = l;
-            if (jf < 0) break;
-            if (round >= kZFixRounds) {
-                st.stop = true;
-                break;
-            }
-            N.fix_rounds++;
-            const uint32_t e = x[jf - 1];
-            for (int l = 0; l < kZLanes; l++)
-                if (kz_fix<C>(w, sb, l, nb, bm[l], sexit[l], jf, e, a[l], x[l])) (g_adversarial ? N.rewalks_adversarial : N.rewalks)++;
+        const KzWin w = emu_walk<C>(wv, in, nb, sb, sb, true, sb, es);
+        if (!wv.settled) {
+            st.stop = true;
+            break;
         }
-        if (st.stop) break;
         KgSum r[kZLanes];
-        for (int l = 0; l < kZLanes; l++) r[l] = kg_sum<C>(w, sb, l, nb, a[l], x[l], lim32, limit);
+        for (int l = 0; l < kZLanes; l++) r[l] = kg_sum<C>(w, sb, l, nb, wv.a[l], wv.x[l], lim32, limit);
         for (int l = 0; l < kZLanes && !st.stop; l++) {  // (the kernel: the prefix up to each event, then kg_cuts on every lane)
             st.total += r[l].out;
             st.maxd = r[l].maxd > st.maxd ? r[l].maxd : st.maxd;
             if (r[l].fl == 0) continue;
             N.events++;
             const uint32_t before = st.ncut;
-            kg_cuts<C>(w, sb, l, nb, r[l].epos, x[l], lim32, limit, st, cut);
+            kg_cuts<C>(w, sb, l, nb, r[l].epos, wv.x[l], lim32, limit, st, cut);
             if (st.ncut - before >= 2) N.packed_chunk++;
         }
-        sb = x[kZLanes - 1];
+        sb = wv.x[kZLanes - 1];
     }
-    std::free(stage);
-    std::free(bm);
+    N.fix_rounds += es.fix_rounds;
+    (g_adversarial ? N.rewalks_adversarial : N.rewalks) += es.rewalks;
     wk.stop = st.stop;
     wk.total = st.total;
     return wk;
@@ -190,12 +98,9 @@ Walk emulate(const uint8_t *in, uint64_t nb64, int64_t limit) {
 // The same chain walked by one lane from the stream's start to its end.
 Walk serial(const Bytes &s, int64_t limit) {
     using namespace ez;
-    Bytes z(s);
-    z.insert(z.end(), 32, 0);
-    const KzWin w{z.data(), 0};
-    const int32_t lim32 = limit == 0 || limit > 0x7fffffff ? 0x7fffffff : (int32_t)limit;
+    const Padded at(s);
     Walk wk;
-    const KgState st = kg_serial([&](uint32_t p) { return kz_at(w, p); }, (uint32_t)s.size(), lim32, limit,
+    const KgState st = kg_serial([&](uint32_t p) { return at(p); }, (uint32_t)s.size(), k2_lim32(limit), limit,
                                  [&](uint32_t, uint32_t pos, uint64_t out) { wk.cuts.push_back(std::make_pair(pos, out)); });
     wk.stop = st.stop;
     wk.total = st.total;
@@ -203,30 +108,9 @@ Walk serial(const Bytes &s, int64_t limit) {
 }
 
 // the oracle's Reader on b: its output and its error (OR_OK on a clean end)
-Bytes g_out;
 int oracle(const uint8_t *b, size_t n, int64_t limit, Bytes &out) {
-    int64_t olen = 0, breaks = 0;
-    int err;
-    if (limit == 0) {
-        err = or_decompress(b, (int64_t)n, 1 << 16, g_out.data(), (int64_t)g_out.size(), &olen, &breaks);
-    } else {  // or_decompress's loop, with the limit set
-        or_reader *r = or_reader_new_bytes(b, (int64_t)n);
-        or_reader_set(r, limit, 1 << 16, 0, 0);
-        for (;;) {
-            int64_t got = 0;
-            if ((size_t)olen + (1 << 16) > g_out.size()) std::exit(2);
-            err = or_reader_read(r, g_out.data() + olen, 1 << 16, &got);
-            olen += got;
-            if (err == OR_EBREAK) continue;
-            if (err == OR_EOF) err = 0;
-            if (err != 0 || got == 0) break;
-        }
-        or_reader_free(r);
-    }
-    if (err == OR_ESHORTBUF && (size_t)olen + (1 << 16) > g_out.size()) {
-        std::printf("the check's output buffer is too small\n");
-        std::exit(2);
-    }
+    int64_t olen = 0;
+    const int err = k2check::oracle(b, n, limit, olen);
     out.assign(g_out.begin(), g_out.begin() + olen);
     return err;
 }
@@ -315,9 +199,8 @@ Bytes resets_body(size_t n, size_t phase) {
     return b;
 }
 Bytes headers_body(size_t n, size_t phase) {
-    static const uint8_t h[9] = {0x80, 0x02, 'e', 'a', 'z', 'y', 0x80, 0x10, 0x14};
     Bytes b;
-    for (size_t k = 0; k < n; k++) b.push_back(h[(k + phase) % 9]);
+    for (size_t k = 0; k < n; k++) b.push_back(kHdr[(k + phase) % 9]);
     return b;
 }
 
@@ -604,7 +487,7 @@ int main(int argc, char **argv) {
         }
     }
     if (g_dump) std::fclose(g_dump);
-#define P(f) std::printf("%-20s %llu\n", #f, (unsigned long long)N.f)
+#define P(f) K2_COUNT(N, 20, f)
     P(streams); P(cuts_found); P(with_cuts); P(stops); P(stops_with_cuts); P(seam_chunk); P(seam_super); P(packed); P(packed_chunk); P(empty_segment);
     P(header_only); P(metas_cut); P(pad_cut); P(break_cut); P(adversarial); P(fix_rounds); P(rewalks); P(rewalks_adversarial); P(lit_enter);
     P(windows); P(overflow_stop); P(zero_reach); P(err_magic); P(err_ver); P(err_meta); P(err_limit); P(trunc_in_seg); P(trunc_joined);

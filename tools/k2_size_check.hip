@@ -1,6 +1,6 @@
 // Host check of K2z's per-lane steps (eazy_amd/csrc/ez_k2_size.h): the same source, compiled for the
-// CPU and run over 64 emulated lanes exactly as the kernel runs them (ez_decompress_size.hip: stage,
-// speculate, verify and re-walk, sum, reduce, the end checks), for every chunk size, compared per
+// CPU and run over 64 emulated lanes exactly as the kernel runs them (ez_decompress_size.hip: the
+// wave's walk of a super-block, sum, reduce, the end checks), for every chunk size, compared per
 // stream with the oracle's Reader (oracle/eazy_oracle.c, or_decompress):
 //   a stream the Reader reads to EOF without an error is taken, with the Reader's output length,
 //   unless it holds a form the fast parse hands over by design; every other stream is handed over.
@@ -17,20 +17,14 @@
 //  - padding runs of 1 to 40 bytes across seams and at the stream's end;
 //  - forms handed over by design (a MetaReset after output, a wide meta);
 //  - every stream cut at each of its last 27 bytes.
-// The staged bytes past what the kernel stages are poisoned, and the buffers are exactly as long as
-// the kernel's, so a sanitizer build of this program shows a step reading outside them.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+// The builder, the serial walk, the oracle call and the wave's walk of a super-block (emu_walk, the
+// mirror of kz_walk) are tools/k2_check_common.h's; here are the kernel's loop over a stream around
+// them, the stream lists, and the proof that kz_spec's known-entry form is the super-block's.
+#include "k2_check_common.h"
 
-#include "../eazy_amd/csrc/ez_k2_size.h"
-#include "../oracle/eazy_oracle.h"
+using namespace k2check;
 
 namespace {
-
-typedef std::vector<uint8_t> Bytes;
 
 struct Counts {
     uint64_t streams, taken, handed_error, handed_design, seam_chunk, seam_super, lit_enter, lit_skip, adversarial, fix_rounds, rewalks, rewalks_adversarial, pad_seam,
@@ -38,196 +32,84 @@ struct Counts {
 } N;
 bool g_adversarial;  // the stream under check is one built to keep speculation off the true chain
 
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-uint64_t rnd() {  // xorshift64*, fixed seed
-    g_rng ^= g_rng >> 12;
-    g_rng ^= g_rng << 25;
-    g_rng ^= g_rng >> 27;
-    return g_rng * 0x2545f4914f6cdd1dull;
-}
-
-// ---- the Encoder
-void put(Bytes &v, const uint8_t *p, size_t n) { v.insert(v.end(), p, p + n); }
-void tag(Bytes &v, int tg, int64_t l) {
-    uint8_t t[32];
-    size_t n = 0;
-    if (or_enc_tag(t, &n, tg, l)) std::exit(2);
-    put(v, t, n);
-}
-void offset(Bytes &v, int64_t d, int64_t l) {
-    uint8_t t[32];
-    size_t n = 0;
-    if (or_enc_offset(t, &n, d, l)) std::exit(2);
-    put(v, t, n);
-}
-void lit_rnd(Bytes &v, int64_t n) {
-    tag(v, 0x00, n);
-    for (int64_t k = 0; k < n; k++) v.push_back((uint8_t)rnd());
-}
-void cpy(Bytes &v, int64_t d, int64_t n) {
-    tag(v, 0x80, n);
-    offset(v, d, n);
-}
-void cpy_long(Bytes &v, int64_t d, int64_t n) {  // the long prefix with a distance that does not need it
-    tag(v, 0x80, n);
-    v.push_back(0xff);
-    offset(v, d, 0);
-}
-void meta(Bytes &v, int64_t m, const char *arg, int n) {
-    uint8_t t[32];
-    size_t k = 0;
-    if (or_enc_meta(t, &k, m, n)) std::exit(2);
-    put(v, t, k);
-    put(v, (const uint8_t *)arg, (size_t)n);
-}
-const uint8_t kHdr[9] = {0x80, 0x02, 'e', 'a', 'z', 'y', 0x80, 0x10, 0x14};  // magic, reset to a 1 MiB window
-void hdr(Bytes &v) { put(v, kHdr, sizeof kHdr); }
-
-// short literals and copies up to exactly `target` bytes of stream
-void fill_to(Bytes &v, size_t target) {
-    while (v.size() < target) {
-        const size_t left = target - v.size();
-        if (left == 1) {
-            v.push_back(0);  // (one byte: padding)
-        } else if (left <= 100) {
-            lit_rnd(v, (int64_t)left - 1);
-        } else if (rnd() % 3 == 0) {
-            cpy(v, 1 + (int64_t)(rnd() % 200), 4 + (int64_t)(rnd() % 60));
-        } else {
-            lit_rnd(v, 1 + (int64_t)(rnd() % 60));
-        }
+// The speculative step as it was before the parts route's form (known, e) took its place, lane 0
+// starting at sb and every other lane warming up from the chunk before its own: the reference that
+// holds kz_spec / kz_entry / kz_verify with (known = true, e = sb) to the same bitmaps, entries and
+// exits on every super-block of every stream here.
+template <int C>
+uint32_t ref_spec(const ez::KzWin &w, uint32_t sb, int lane, uint32_t nb, uint32_t *bm) {
+    using namespace ez;
+    uint32_t c0, ce;
+    kz_chunk<C>(sb, lane, nb, c0, ce);
+    for (int k = 0; k < C / 32; k++) bm[k] = 0;
+    if (c0 >= nb) return c0;
+    uint32_t p = lane == 0 ? sb : c0 - C;
+    while (p < c0) p = kz_next(w, p, nb);
+    while (p < ce) {
+        bm[(p - c0) >> 5] |= 1u << ((p - c0) & 31);
+        p = kz_next(w, p, nb);
     }
+    return p;
 }
-void tail3(Bytes &v) {
-    lit_rnd(v, 5);
-    cpy(v, 3, 9);
-    lit_rnd(v, 2);
-}
-
-struct Form {
-    const char *name;
-    Bytes b;
-    bool big_first;  // needs a 70,000-byte literal before it
-};
-std::vector<Form> forms() {
-    std::vector<Form> f;
-    auto add = [&](const char *name, bool big) -> Bytes & {
-        f.push_back(Form{name, Bytes(), big});
-        return f.back().b;
-    };
-    lit_rnd(add("lit_len0", false), 50);
-    lit_rnd(add("lit_len1", false), 200);
-    lit_rnd(add("lit_len2", false), 1000);
-    lit_rnd(add("lit_len4", false), 70000);
-    cpy(add("cpy_plain", false), 30, 20);
-    cpy(add("cpy_off1", false), 320, 20);
-    cpy(add("cpy_off2", false), 720, 20);
-    cpy(add("cpy_len1_off1", false), 500, 200);
-    cpy(add("cpy_len2", false), 510, 500);
-    cpy(add("cpy_off4", true), 66044 + 20 + 100, 20);
-    cpy(add("cpy_len4_run", false), 1, 70000);
-    cpy_long(add("cpy_long", false), 40, 20);
-    cpy(add("zero_region", false), 0, 64);
-    meta(add("break", false), 3 << 3, "", 0);
-    meta(add("ver", false), 1 << 3, "\x00", 1);
-    meta(add("magic", false), 0 << 3, "eazy", 4);
-    static const int pads[5] = {1, 15, 16, 17, 40};
-    static const char *pad_names[5] = {"pad1", "pad15", "pad16", "pad17", "pad40"};
-    for (int k = 0; k < 5; k++) add(pad_names[k], false).assign((size_t)pads[k], 0);
-    return f;
+template <int C>
+void check_unified(const EmuWave<C> &wv, const ez::KzWin &w, uint32_t sb, uint32_t nb) {
+    using namespace ez;
+    uint32_t bm[C / 32], prev = 0;
+    for (int l = 0; l < kZLanes; l++) {
+        const uint32_t sexit = ref_spec<C>(w, sb, l, nb, bm);
+        const uint32_t a = l == 0 ? sb : prev;
+        const uint32_t x = l == 0 ? sexit : kz_verify<C>(w, sb, l, nb, bm, sexit, a);
+        if (sexit != wv.sexit[l] || a != wv.a0[l] || x != wv.x0[l] || std::memcmp(bm, wv.bm[l], sizeof bm) != 0) {
+            std::printf("MISMATCH super-block at %u, lane %d (chunk %d): kz_spec with a known entry is not the super-block form\n", sb, l, C);
+            std::exit(1);
+        }
+        prev = sexit;
+    }
 }
 
 // ---- the kernel's loop over a stream, 64 lanes emulated in order
-struct Result {
-    bool taken;
-    uint64_t size;
-};
-
 template <int C>
 Result emulate(const uint8_t *in, uint64_t nb64) {
     using namespace ez;
-    constexpr int W = C / 32;
     bool bad = nb64 >= (1ull << 31);
     const uint32_t nb = bad ? 0u : (uint32_t)nb64;
     uint32_t sb = 0, maxd = 0;
     uint64_t total = 0;
     int32_t bsl = -1;
-    // exactly the kernel's LDS: an access outside them is one outside the kernel's
-    uint8_t *stage = (uint8_t *)std::malloc(kz_stage_bytes(C));
-    uint32_t(*bm)[W] = (uint32_t(*)[W])std::malloc(sizeof(uint32_t) * W * kZLanes);
-    uint32_t sexit[kZLanes], a[kZLanes], x[kZLanes];
+    EmuWave<C> wv(kz_stage_bytes(C));
+    EmuStats st{};
     while (!bad && sb < nb) {
         N.superblocks++;
-        const uint32_t need = nb - sb + 16 < kz_stage_bytes(C) ? nb - sb + 16 : kz_stage_bytes(C);
-        std::memset(stage, 0xcc, kz_stage_bytes(C));  // (what the kernel leaves from earlier: never read)
-        for (uint32_t o = 0; o < need; o += 16)
-            for (uint32_t k = 0; k < 16; k++) stage[o + k] = sb + o + k < nb ? in[sb + o + k] : 0;
-        const KzWin w{stage, sb};
-        for (int l = 0; l < kZLanes; l++) sexit[l] = kz_spec<C>(w, sb, l, nb, bm[l]);
-        for (int l = 0; l < kZLanes; l++) a[l] = l == 0 ? sb : sexit[l - 1];
-        for (int l = 0; l < kZLanes; l++) {
-            x[l] = l == 0 ? sexit[0] : kz_verify<C>(w, sb, l, nb, bm[l], sexit[l], a[l]);
-            uint32_t c0, ce;
-            kz_chunk<C>(sb, l, nb, c0, ce);
-            if (l > 0 && a[l] >= ce) N.passthrough++;
-            else if (l > 0 && x[l] == sexit[l]) N.merged++;
+        const KzWin w = emu_walk<C>(wv, in, nb, sb, sb, true, sb, st);
+        check_unified<C>(wv, w, sb, nb);
+        if (!wv.settled) {
+            bad = true;
+            break;
         }
-        for (int round = 0;; round++) {
-            int jf = -1;
-            for (int l = 1; l < kZLanes && jf < 0; l++)
-                if (a[l] != x[l - 1]) jf = l;
-            if (jf < 0) break;
-            if (round >= kZFixRounds) {
-                bad = true;
-                break;
-            }
-            N.fix_rounds++;
-            const uint32_t e = x[jf - 1];
-            for (int l = 0; l < kZLanes; l++)
-                if (kz_fix<C>(w, sb, l, nb, bm[l], sexit[l], jf, e, a[l], x[l])) (g_adversarial ? N.rewalks_adversarial : N.rewalks)++;
-        }
-        if (bad) break;
         uint64_t run = 0;
         for (int l = 0; l < kZLanes; l++) {
-            const KzSum r = kz_sum<C>(w, sb, l, nb, a[l], x[l], 0x7fffffff, 0);
+            const KzSum r = kz_sum<C>(w, sb, l, nb, wv.a[l], wv.x[l], 0x7fffffff, 0);
             if ((r.fl & kZBad) || kz_reset_bad(r.fl, total + run)) bad = true;
             if (r.fl & kZReset) bsl = (int32_t)((r.fl >> 8) & 0xff);
             run += r.out;
             maxd = r.maxd > maxd ? r.maxd : maxd;
         }
         total += run;
-        if (x[kZLanes - 1] - sb > (uint32_t)kZLanes * C + 65536) N.lit_skip++;
-        sb = x[kZLanes - 1];
+        if (wv.x[kZLanes - 1] - sb > (uint32_t)kZLanes * C + 65536) N.lit_skip++;
+        sb = wv.x[kZLanes - 1];
     }
     if (!bad) bad = !kz_end_ok(sb, nb, total, bsl, maxd);
-    std::free(stage);
-    std::free(bm);
+    N.fix_rounds += st.fix_rounds;
+    (g_adversarial ? N.rewalks_adversarial : N.rewalks) += st.rewalks;
+    N.passthrough += st.passthrough;
+    N.merged += st.merged;
     return Result{!bad, total};
 }
 
-// The same chain walked by one lane from the stream's start to its end (kz_serial, which is also the
-// lane-per-stream kernel's walk): the result the chunked walk must reproduce whatever the seams and
-// the speculation do.
-Result serial(const Bytes &s) {
-    using namespace ez;
-    Bytes z(s);
-    z.insert(z.end(), 32, 0);
-    const KzWin w{z.data(), 0};
-    uint64_t total = 0;
-    const bool ok = kz_serial([&](uint32_t p) { return kz_at(w, p); }, (uint32_t)s.size(), 0x7fffffff, 0, total);
-    return Result{ok, total};
-}
-
-Bytes g_out;
-
 // one stream against the oracle, for both chunk sizes; design: it holds a form handed over by design
 bool check_one(const std::string &name, const Bytes &s, bool design, bool cut) {
-    int64_t olen = 0, breaks = 0;
-    const int err = or_decompress(s.data(), (int64_t)s.size(), 1 << 16, g_out.data(), (int64_t)g_out.size(), &olen, &breaks);
-    if (err == OR_ESHORTBUF) {
-        std::printf("the check's output buffer is too small for %s\n", name.c_str());
-        std::exit(2);
-    }
+    int64_t olen = 0;
+    const int err = oracle(s.data(), s.size(), 0, olen);
     // A stream cut inside a meta or a token's header may still read to EOF without an error (a lone
     // 0x80 at the end: continueMetaTag's short buffer leaves i at the input's end, reader.go:272-280,
     // which Read takes for a clean end); k2_scan hands a step past the input over, so such a cut is
@@ -385,7 +267,7 @@ int main(int argc, char **argv) {
         lit_rnd(wm, 3);
         check("wide meta", wm, true);
     }
-#define P(f) std::printf("%-18s %llu\n", #f, (unsigned long long)N.f)
+#define P(f) K2_COUNT(N, 18, f)
     P(streams); P(taken); P(handed_error); P(handed_design); P(seam_chunk); P(seam_super); P(lit_enter); P(lit_skip); P(adversarial);
     P(fix_rounds); P(rewalks); P(rewalks_adversarial); P(pad_seam); P(pad_tail); P(cuts); P(cuts_taken); P(cuts_handed_ok); P(superblocks); P(passthrough); P(merged); P(chunk64); P(chunk256); P(chunk1024);
     std::printf("ok\n");

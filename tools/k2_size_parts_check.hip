@@ -24,20 +24,14 @@
 //    stream it leaves to the wave route gets no parts, and the same result from tools/k2_size_check.hip's walk);
 //  - a batch of these streams with empty ones and streams shorter than a chunk between them, laid
 //    out and searched as the kernels do.
-// The staged bytes past what the kernel stages are poisoned, and the buffers are exactly as long as
-// the kernel's, so a sanitizer build of this program shows a step reading outside them.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+// The builder, the serial walk, the oracle call and the wave's walk of a part (emu_walk, the mirror of
+// kz_walk) are tools/k2_check_common.h's; here are the part's record, the part layout and the in-order
+// pass around them, and the stream lists.
+#include "k2_check_common.h"
 
-#include "../eazy_amd/csrc/ez_k2_parts.h"
-#include "../oracle/eazy_oracle.h"
+using namespace k2check;
 
 namespace {
-
-typedef std::vector<uint8_t> Bytes;
 
 struct Counts {
     uint64_t streams, taken, handed_error, handed_design, seam_part, lit_within, lit_one_part, lit_many_parts, adversarial, parts, joined, passed, walked,
@@ -46,154 +40,21 @@ struct Counts {
 } N;
 bool g_adversarial;  // the stream under check is one built to keep speculation off the true chain
 
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-uint64_t rnd() {  // xorshift64*, fixed seed
-    g_rng ^= g_rng >> 12;
-    g_rng ^= g_rng << 25;
-    g_rng ^= g_rng >> 27;
-    return g_rng * 0x2545f4914f6cdd1dull;
-}
-
-// ---- the Encoder
-void put(Bytes &v, const uint8_t *p, size_t n) { v.insert(v.end(), p, p + n); }
-void tag(Bytes &v, int tg, int64_t l) {
-    uint8_t t[32];
-    size_t n = 0;
-    if (or_enc_tag(t, &n, tg, l)) std::exit(2);
-    put(v, t, n);
-}
-void offset(Bytes &v, int64_t d, int64_t l) {
-    uint8_t t[32];
-    size_t n = 0;
-    if (or_enc_offset(t, &n, d, l)) std::exit(2);
-    put(v, t, n);
-}
-void lit_rnd(Bytes &v, int64_t n) {
-    tag(v, 0x00, n);
-    for (int64_t k = 0; k < n; k++) v.push_back((uint8_t)rnd());
-}
-void cpy(Bytes &v, int64_t d, int64_t n) {
-    tag(v, 0x80, n);
-    offset(v, d, n);
-}
-void cpy_long(Bytes &v, int64_t d, int64_t n) {  // the long prefix with a distance that does not need it
-    tag(v, 0x80, n);
-    v.push_back(0xff);
-    offset(v, d, 0);
-}
-void meta(Bytes &v, int64_t m, const char *arg, int n) {
-    uint8_t t[32];
-    size_t k = 0;
-    if (or_enc_meta(t, &k, m, n)) std::exit(2);
-    put(v, t, k);
-    put(v, (const uint8_t *)arg, (size_t)n);
-}
-const uint8_t kHdr[9] = {0x80, 0x02, 'e', 'a', 'z', 'y', 0x80, 0x10, 0x14};  // magic, reset to a 1 MiB window
-void hdr(Bytes &v) { put(v, kHdr, sizeof kHdr); }
-
-// short literals and copies up to exactly `target` bytes of stream
-void fill_to(Bytes &v, size_t target) {
-    while (v.size() < target) {
-        const size_t left = target - v.size();
-        if (left == 1) {
-            v.push_back(0);  // (one byte: padding)
-        } else if (left <= 100) {
-            lit_rnd(v, (int64_t)left - 1);
-        } else if (rnd() % 3 == 0) {
-            cpy(v, 1 + (int64_t)(rnd() % 200), 4 + (int64_t)(rnd() % 60));
-        } else {
-            lit_rnd(v, 1 + (int64_t)(rnd() % 60));
-        }
-    }
-}
-void tail3(Bytes &v) {
-    lit_rnd(v, 5);
-    cpy(v, 3, 9);
-    lit_rnd(v, 2);
-}
-
-struct Form {
-    const char *name;
-    Bytes b;
-    bool big_first;  // needs a 70,000-byte literal before it
-};
-std::vector<Form> forms() {
-    std::vector<Form> f;
-    auto add = [&](const char *name, bool big) -> Bytes & {
-        f.push_back(Form{name, Bytes(), big});
-        return f.back().b;
-    };
-    lit_rnd(add("lit_len0", false), 50);
-    lit_rnd(add("lit_len1", false), 200);
-    lit_rnd(add("lit_len2", false), 1000);
-    lit_rnd(add("lit_len4", false), 70000);
-    cpy(add("cpy_plain", false), 30, 20);
-    cpy(add("cpy_off1", false), 320, 20);
-    cpy(add("cpy_off2", false), 720, 20);
-    cpy(add("cpy_len1_off1", false), 500, 200);
-    cpy(add("cpy_len2", false), 510, 500);
-    cpy(add("cpy_off4", true), 66044 + 20 + 100, 20);
-    cpy(add("cpy_len4_run", false), 1, 70000);
-    cpy_long(add("cpy_long", false), 40, 20);
-    cpy(add("zero_region", false), 0, 64);
-    meta(add("break", false), 3 << 3, "", 0);
-    meta(add("ver", false), 1 << 3, "\x00", 1);
-    meta(add("magic", false), 0 << 3, "eazy", 4);
-    static const int pads[5] = {1, 15, 16, 17, 40};
-    static const char *pad_names[5] = {"pad1", "pad15", "pad16", "pad17", "pad40"};
-    for (int k = 0; k < 5; k++) add(pad_names[k], false).assign((size_t)pads[k], 0);
-    return f;
-}
-
 // ---- the kernels' steps, lanes and parts emulated in order
-struct Result {
-    bool taken;
-    uint64_t size;
-};
-
 // part_walk of ez_decompress_parts.hip: one part by 64 lanes
 template <int C>
 ez::KpRec emu_part(const uint8_t *in, uint32_t nb, uint32_t ps, bool known, uint32_t e) {
     using namespace ez;
-    constexpr int W = C / 32;
-    // exactly the kernel's LDS: an access outside them is one outside the kernel's
-    uint8_t *stage = (uint8_t *)std::malloc(kp_stage_bytes(C));
-    uint32_t(*bm)[W] = (uint32_t(*)[W])std::malloc(sizeof(uint32_t) * W * kZLanes);
-    uint32_t sexit[kZLanes], first[kZLanes], a[kZLanes], x[kZLanes];
-    const uint32_t sbase = kp_stage_base(ps, C);
-    const uint32_t pe = nb - ps > kp_part_bytes(C) ? ps + kp_part_bytes(C) : nb;
-    const uint32_t need = pe + 16 - sbase;
-    std::memset(stage, 0xcc, kp_stage_bytes(C));  // (what the kernel leaves from earlier: never read)
-    for (uint32_t o = 0; o < need; o += 16)
-        for (uint32_t k = 0; k < 16; k++) stage[o + k] = sbase + o + k < nb ? in[sbase + o + k] : 0;
-    const KzWin w{stage, sbase};
-    for (int l = 0; l < kZLanes; l++) sexit[l] = kp_spec<C>(w, ps, l, nb, known, e, bm[l], first[l]);
-    for (int l = 0; l < kZLanes; l++) a[l] = kp_entry(l, ps, C, known, e, first[l], l ? sexit[l - 1] : 0);
-    for (int l = 0; l < kZLanes; l++) x[l] = kz_verify<C>(w, ps, l, nb, bm[l], sexit[l], a[l]);
-    bool settled = true;
-    for (int round = 0;; round++) {
-        int jf = -1;
-        for (int l = 1; l < kZLanes && jf < 0; l++)
-            if (a[l] != x[l - 1]) jf = l;
-        if (jf < 0) break;
-        if (round >= kZFixRounds) {
-            settled = false;
-            break;
-        }
-        const uint32_t ex = x[jf - 1];
-        for (int l = 0; l < kZLanes; l++) kz_fix<C>(w, ps, l, nb, bm[l], sexit[l], jf, ex, a[l], x[l]);
-    }
-    KpRec rec{0, kPNoEntry, 0, 0, 0};
-    if (settled) {
-        KzSum acc{0, 0, 0};
-        for (int l = 0; l < kZLanes; l++) kp_append(acc, kz_sum<C>(w, ps, l, nb, a[l], x[l], 0x7fffffff, 0));
-        rec = KpRec{acc.out, a[0], x[kZLanes - 1], acc.maxd, acc.fl};
-    } else {
+    EmuWave<C> wv(kp_stage_bytes(C));
+    EmuStats st{};
+    const KzWin w = emu_walk<C>(wv, in, nb, kp_stage_base(ps, C), ps, known, e, st);
+    if (!wv.settled) {
         N.unsettled++;
+        return KpRec{0, kPNoEntry, 0, 0, 0};
     }
-    std::free(stage);
-    std::free(bm);
-    return rec;
+    KzSum acc{0, 0, 0};
+    for (int l = 0; l < kZLanes; l++) kp_append(acc, kz_sum<C>(w, ps, l, nb, wv.a[l], wv.x[l], 0x7fffffff, 0));
+    return KpRec{acc.out, wv.a[0], wv.x[kZLanes - 1], acc.maxd, acc.fl};
 }
 
 // kp_init, kp_first and kp_order over a batch: the records are exactly as many as the layout says
@@ -260,36 +121,18 @@ std::vector<Result> emulate(const std::vector<const Bytes *> &ins) {
     return out;
 }
 
-// The same chain walked by one lane from the stream's start to its end (kz_serial).
-Result serial(const Bytes &s) {
-    using namespace ez;
-    Bytes z(s);
-    z.insert(z.end(), 32, 0);
-    const KzWin w{z.data(), 0};
-    uint64_t total = 0;
-    const bool ok = kz_serial([&](uint32_t p) { return kz_at(w, p); }, (uint32_t)s.size(), 0x7fffffff, 0, total);
-    return Result{ok, total};
-}
-
-Bytes g_out;
 std::vector<Bytes> g_kept;  // some of the streams, for the batch at the end
 
 // one stream against the oracle, for both chunk sizes; design: it holds a form handed over by design
 bool check_one(const std::string &name, const Bytes &s, bool design, bool cut) {
-    int64_t olen = 0, breaks = 0;
-    const int err = or_decompress(s.data(), (int64_t)s.size(), 1 << 16, g_out.data(), (int64_t)g_out.size(), &olen, &breaks);
-    if (err == OR_ESHORTBUF) {
-        std::printf("the check's output buffer is too small for %s\n", name.c_str());
-        std::exit(2);
-    }
+    int64_t olen = 0;
+    const int err = oracle(s.data(), s.size(), 0, olen);
     // (a cut inside a header may still read to EOF without an error, and k2_scan hands it over:
     // tools/k2_size_check.hip, cuts_handed_ok.  The serial walk says which.)
     const Result one = serial(s);
     if (!cut && !s.empty()) {  // the automatic route's probe: which route would size this stream (the result is the same)
-        Bytes z(s);
-        z.insert(z.end(), 32, 0);
-        const ez::KzWin w{z.data(), 0};
-        (ez::kp_probe_wave([&](uint32_t p) { return ez::kz_at(w, p); }, (uint32_t)s.size()) ? N.probe_wave : N.probe_parts)++;
+        const Padded at(s);
+        (ez::kp_probe_wave([&](uint32_t p) { return at(p); }, (uint32_t)s.size()) ? N.probe_wave : N.probe_parts)++;
     }
     const bool want_taken = cut ? one.taken : err == 0 && !design;
     if (cut && !one.taken && err == 0) N.cuts_handed_ok++;
@@ -474,7 +317,7 @@ int main() {
             }
         }
     }
-#define P(f) std::printf("%-20s %llu\n", #f, (unsigned long long)N.f)
+#define P(f) K2_COUNT(N, 20, f)
     P(streams); P(taken); P(handed_error); P(handed_design); P(seam_part); P(lit_within); P(lit_one_part); P(lit_many_parts); P(adversarial);
     P(parts); P(joined); P(passed); P(walked); P(walked_adversarial); P(unsettled); P(garbage_bad); P(garbage_bad_taken); P(pad_seam); P(reset_late_part);
     P(cuts); P(cuts_taken); P(cuts_handed_ok); P(batch_streams); P(batch_short); P(batch_parts); P(probe_wave); P(probe_parts); P(chunk256); P(chunk1024);
