@@ -136,6 +136,7 @@ def _lib():
     L.ez_decompress_batch.argtypes = [i64, vp, vp, vp]
     L.ez_decompressed_size_batch.argtypes = [i64, vp, vp, vp]
     L.ez_decompressed_size_chunk.argtypes = [C.c_uint64]
+    L.ez_decompressed_size_segs_last.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.ez_segments_workspace.restype = sz
     L.ez_segments_workspace.argtypes = [C.c_uint64]
     L.ez_stream_segments_batch.argtypes = [i64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp]
@@ -958,6 +959,15 @@ def decompressed_size_parts_last() -> tuple[int, int, int]:
     return int(c[0]), int(c[1]), int(c[2])
 
 
+def decompressed_size_segs_last(workspace, count: int) -> tuple[int, int, int]:
+    """Of a decompressed_sizes call with this workspace over count streams, after its stream was
+    synchronised: streams the fast kernels handed over, those K2g's walk sized behind them
+    (concatenated streams: a MetaReset after output), those it handed on to the exact decoder."""
+    c = (C.c_uint64 * 3)()
+    _check(_lib().ez_decompressed_size_segs_last(workspace.data_ptr(), count, c))
+    return int(c[0]), int(c[1]), int(c[2])
+
+
 def decompressed_sizes(comp, comp_off, block_size_limit: int = 0, sizes=None, status=None, workspace=None,
                        exact_only: bool = False, stream=None, max_len: int = 0, in_bytes: int = 0):
     """K2z: what decompress_batch would report for every stream comp[comp_off[s]:comp_off[s+1]]
@@ -1060,8 +1070,10 @@ def decompress_batch_sized(comp, comp_off, block_size_limit: int = 0, stream=Non
     """Decode a batch whose decoded lengths the caller does not know -> (out, out_off, sizes,
     status).  The sizes come from decompressed_sizes; the slots are laid out on the device (each
     size rounded up to 16 bytes), the total and the largest slot are read back in one transfer
-    (which waits for the stream), and decompress_batch decodes with those as its hints.  sizes
-    and status are the decode's."""
+    (which waits for the stream), and decompress_batch decodes with those as its hints.  The same
+    transfer carries how many concatenated streams (a MetaReset after output) the query sized by
+    K2g's walk: where there are any, decompress_batch_segmented decodes instead, so that their
+    segments take the fast decoders too.  sizes and status are the decode's."""
     import torch
 
     _need_cuda(comp, comp_off)
@@ -1071,17 +1083,22 @@ def decompress_batch_sized(comp, comp_off, block_size_limit: int = 0, stream=Non
 
     ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()  # (the torch steps on it too)
     with ctx:
-        need, _ = decompressed_sizes(comp, comp_off, block_size_limit, stream=stream)
+        ws = torch.empty(_lib().ez_decompress_workspace(count), dtype=torch.uint8, device=dev)
+        need, _ = decompressed_sizes(comp, comp_off, block_size_limit, workspace=ws, stream=stream)
         slot = (need + 15) & ~15
         out_off = torch.zeros(count + 1, dtype=torch.int64, device=dev)
         torch.cumsum(slot, 0, out=out_off[1:])
-        total = largest = in_bytes = 0
+        total = largest = in_bytes = joined = 0
         if count:
-            back = torch.stack([out_off[-1], slot.max(), comp_off[-1] - comp_off[0]]).cpu()
-            total, largest, in_bytes = (int(v) for v in back)
+            sized = ws[4 * (count + 2) : 4 * (count + 3)].view(torch.int32)[0]  # (ez_decompressed_size_segs_last's counts[1])
+            back = torch.stack([out_off[-1], slot.max(), comp_off[-1] - comp_off[0], sized.to(torch.int64)]).cpu()
+            total, largest, in_bytes, joined = (int(v) for v in back)
         out = torch.empty(total + 16, dtype=torch.uint8, device=dev)
-        _, sizes, status = decompress_batch(comp, comp_off, out_off, block_size_limit, out=out, stream=stream, max_len=largest,
-                                            in_bytes=in_bytes, out_bytes=total)
+        if joined:
+            _, sizes, status = decompress_batch_segmented(comp, comp_off, out_off, block_size_limit, out=out, stream=stream)
+        else:
+            _, sizes, status = decompress_batch(comp, comp_off, out_off, block_size_limit, out=out, workspace=ws, stream=stream,
+                                                max_len=largest, in_bytes=in_bytes, out_bytes=total)
     return out, out_off, sizes, status
 
 

@@ -784,6 +784,25 @@ inline Err DecompressBatchSegmented(int64_t block_size_limit, const ez_batch &b,
 // ez_segments_last: of the last DecompressBatchSegmented call, {segments decoded, handed to the exact
 // decoder, query retries}
 inline Err SegmentsLast(uint64_t counts[3]) { return (Err)ez_segments_last(counts); }
+// ez_decompressed_size_segs_last: of a DecompressedSizeBatch call with this workspace over count
+// streams, whose stream the caller has synchronised, {streams the fast kernels handed over, those K2g's
+// walk sized behind them (concatenated streams), those it handed on to the exact decoder}
+inline Err DecompressedSizeSegsLast(const void *workspace, uint64_t count, uint64_t counts[3]) {
+    const int st = ez_decompressed_size_segs_last(workspace, count, counts);
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: DecompressedSizeSegsLast: workspace and counts are required");
+    return (Err)st;
+}
+// The decode of a batch whose decoded lengths were unknown: the caller ran DecompressedSizeBatch with
+// this workspace, synchronised its stream and laid out b.out_off (and out) from the sizes.  Where that
+// query sized concatenated streams (DecompressedSizeSegsLast's counts[1], read here) the decode is
+// DecompressBatchSegmented's, so that their segments take the fast decoders too; else DecompressBatch's
+// with b's hints.  The same out, out_size and status either way.
+inline Err DecompressBatchSized(int64_t block_size_limit, const ez_batch &b, void *workspace, void *hip_stream) {
+    uint64_t c[3] = {0, 0, 0};
+    const Err e = DecompressedSizeSegsLast(workspace, b.count, c);
+    if (e != Err::OK) return e;
+    return c[1] != 0 ? DecompressBatchSegmented(block_size_limit, b, hip_stream) : DecompressBatch(block_size_limit, b, workspace, hip_stream);
+}
 
 // Host-memory batches over several devices (ez_compress_batch_multi / ez_decompress_batch_multi):
 // bufs[k] is one Write to a fresh NewWriter(block, htable); out[k] gets its compressed bytes,

@@ -320,6 +320,17 @@ extern "C" int ez_decompressed_size_parts_last(uint64_t counts[3]) {
     return EZ_OK;
 }
 
+extern "C" int ez_decompressed_size_segs_last(const void *workspace, uint64_t count, uint64_t counts[3]) {
+    if (!workspace || !counts) return EZ_EINVAL;
+    counts[0] = counts[1] = counts[2] = 0;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    if (count == 0) return EZ_OK;  // (such a query touches no workspace)
+    uint32_t c[3];
+    EZ_HIP(hipMemcpy(c, ez::size_segs_counters((uint32_t *)workspace, count), sizeof c, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) counts[k] = c[k];
+    return EZ_OK;
+}
+
 // ---- K2g: concatenated streams (ez_decompress_segs.hip)
 
 extern "C" size_t ez_segments_workspace(uint64_t count) { return (size_t)ez::segments_workspace_bytes(count); }

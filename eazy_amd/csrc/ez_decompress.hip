@@ -310,8 +310,9 @@ static hipError_t largest_slot(const DecompressArgs &a, hipStream_t st, uint64_t
     return hipSuccess;
 }
 
-// K2z: the decoded sizes.  With a workspace the fast kernel first, its hand-overs to the exact decoder
-// through the slow list as for the other decoders; without one the exact decoder alone.  Dry, both
+// K2z: the decoded sizes.  With a workspace the fast kernel first, its hand-overs through the slow list
+// as for the other decoders: to K2g's stage (k2g_size), which sizes the concatenated streams among
+// them and lists the rest again for the exact decoder; without one the exact decoder alone.  Dry, both
 // ways: it reads every stream to EOF and stores nothing.
 static std::atomic<int> g_last_size_chunk{-1};
 int last_size_chunk() { return g_last_size_chunk; }
@@ -337,7 +338,9 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
         hipLaunchKernelGGL(k2_decompress, dim3((unsigned)grid), dim3(64), 0, st, a);
         return hipGetLastError();
     }
-    hipError_t e = hipMemsetAsync(a.slow, 0, sizeof(uint32_t), st);
+    // (one memset: the first list's length, and behind its entries K2g's counters and the second list's length)
+    uint32_t *second = size_segs_counters(a.slow, a.count) + 2;
+    hipError_t e = hipMemsetAsync(a.slow, 0, (size_t)(second + 1 - a.slow) * sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     CacheLease lease;  // (the parts route's scratch, until the wave route behind it is launched)
     if (pchunk) {
@@ -351,6 +354,9 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
     a.jws_cap = 0;
     g_last_size_chunk = chunk;
     if ((e = launch_size_fast(a, chunk, st)) != hipSuccess) return e;
+    // K2g's walk sizes the concatenated streams of the list; the exact decoder gets the second list
+    if ((e = launch_size_segs(a, max_len, st)) != hipSuccess) return e;
+    a.slow = second;
     const uint64_t exact_grid = a.count < 4096 ? a.count : 4096;
     hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
     return hipGetLastError();

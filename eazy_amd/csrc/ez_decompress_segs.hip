@@ -24,6 +24,8 @@
 //   heads    a thread per stream: each stream's first segment, the kept cuts, the arrays' ends;
 //   fill     the walk again, only for streams with more than kGKeep cuts, which writes them in place.
 // A stream without a Reset after output is walked once.
+// The size query (ez_decompressed_size_batch) runs the same walk in one more kernel, k2g_size, over the
+// streams its fast kernels handed over: the walk's total is a concatenated stream's decoded length.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -39,6 +41,51 @@ namespace ez {
 namespace {
 
 constexpr uint32_t kGKeep = 15;  // cuts the count pass keeps per stream (streams of up to 16 segments are walked once)
+
+// One stream b[0 .. nb) by the whole wave: super-blocks through kz_walk, kg_sum, the in-order prefix and
+// the events in lane order through kg_cuts, which calls cut(i, pos, out) on every lane for cut i.
+// Returns the stream's state and where its chain ended (both wave-uniform).
+struct KgEnd {
+    KgState st;
+    uint32_t end;
+};
+template <int C, class Cut>
+__device__ __forceinline__ KgEnd kg_stream(uint8_t *stage, uint32_t (*bm)[C / 32 + 1], const uint8_t *b, uint32_t nb, int32_t lim32,
+                                           int64_t limit, Cut cut) {
+    const int lane = lane_id();
+    KgState st = kg_start();
+    uint32_t sb = 0;
+    while (!st.stop && sb < nb) {
+        const KzWalk k = kz_walk<C>(stage, bm, b, nb, sb, sb, true, sb);
+        if (!k.settled) {
+            st.stop = true;
+            break;
+        }
+        const KzWin w{stage, sb};
+        const KgSum r = kg_sum<C>(w, sb, lane, nb, k.a, k.x, lim32, limit);
+        const uint64_t io = wscan_add_u64(r.out);
+        uint64_t ev = wballot(r.fl != 0);
+        uint64_t base = 0;  // the prefix taken into the state so far
+        int from = 0;       // the first lane whose distances are not in the state yet
+        while (ev) {
+            const int j = ffs64(ev);
+            ev &= ev - 1;
+            // the lanes before j, and lane j's tokens before its event
+            const uint64_t ioj = __shfl(io, j, kWave);
+            st.total += ioj - base;
+            base = ioj;
+            st.maxd = max(st.maxd, wmax_u32(lane >= from && lane <= j ? r.maxd : 0u));
+            from = j + 1;
+            kg_cuts<C>(w, sb, j, nb, (uint32_t)__shfl((int)r.epos, j, kWave), (uint32_t)__shfl((int)k.x, j, kWave), lim32, limit, st, cut);
+            if (st.stop) break;
+        }
+        if (st.stop) break;
+        st.total += __shfl(io, kWave - 1, kWave) - base;
+        st.maxd = max(st.maxd, wmax_u32(lane >= from ? r.maxd : 0u));
+        sb = __shfl(k.x, kWave - 1, kWave);
+    }
+    return KgEnd{st, sb};
+}
 
 template <int C, bool FILL>
 __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
@@ -72,38 +119,53 @@ __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
                 A.seg_out[g0 + 1 + i] = out < o1 - o0 ? o0 + out : o1;
             }
         };
-        KgState st = kg_start();
-        uint32_t sb = 0;
-        while (!st.stop && sb < nb) {
-            const KzWalk k = kz_walk<C>(stage, bm, b, nb, sb, sb, true, sb);
-            if (!k.settled) {
-                st.stop = true;
-                break;
-            }
-            const KzWin w{stage, sb};
-            const KgSum r = kg_sum<C>(w, sb, lane, nb, k.a, k.x, lim32, limit);
-            const uint64_t io = wscan_add_u64(r.out);
-            uint64_t ev = wballot(r.fl != 0);
-            uint64_t base = 0;  // the prefix taken into the state so far
-            int from = 0;       // the first lane whose distances are not in the state yet
-            while (ev) {
-                const int j = ffs64(ev);
-                ev &= ev - 1;
-                // the lanes before j, and lane j's tokens before its event
-                const uint64_t ioj = __shfl(io, j, kWave);
-                st.total += ioj - base;
-                base = ioj;
-                st.maxd = max(st.maxd, wmax_u32(lane >= from && lane <= j ? r.maxd : 0u));
-                from = j + 1;
-                kg_cuts<C>(w, sb, j, nb, (uint32_t)__shfl((int)r.epos, j, kWave), (uint32_t)__shfl((int)k.x, j, kWave), lim32, limit, st, cut);
-                if (st.stop) break;
-            }
-            if (st.stop) break;
-            st.total += __shfl(io, kWave - 1, kWave) - base;
-            st.maxd = max(st.maxd, wmax_u32(lane >= from ? r.maxd : 0u));
-            sb = __shfl(k.x, kWave - 1, kWave);
+        const KgEnd r = kg_stream<C>(stage, bm, b, nb, lim32, limit, cut);
+        if (!FILL && lane == 0) A.seg_idx[s] = (uint64_t)r.st.ncut + 1;
+    }
+}
+
+// The size query's stage behind K2z (launch_decompress_size): a wave per entry of the list K2z's kernels
+// and the parts route wrote (first: [0] = its length, read here, on the device), grid-stride.  The walk
+// is k2g_walk's with a cut that stores nothing, and kg_end_ok decides at the stream's end: the wave
+// writes out_size[s] = the total and EZ_OK, or appends the stream to the second list for the exact
+// decoder run dry (a stop, an unsettled super-block, 2 GiB or more, a failed end check).  The first
+// list is only read.  ctr: {entries taken, streams sized, the second list: [0] = its length, which is
+// the streams handed on}, zeroed by the launcher.
+template <int C>
+__global__ __launch_bounds__(64) void k2g_size(DecompressArgs A, const uint32_t *first, uint32_t *ctr) {
+    constexpr int W = C / 32;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kz_stage_bytes(C)];
+    __shared__ uint32_t bm[kZLanes][W + 1];  // (+1: the lanes' rows on distinct banks)
+    const uint64_t n = first[0] < A.count ? first[0] : A.count;  // (a list is never longer than the batch: the second one has room for that)
+    const int lane = lane_id();
+    const int64_t limit = A.block_size_limit;
+    const int32_t lim32 = k2_lim32(limit);
+    uint32_t sized = 0;
+    for (uint64_t k = blockIdx.x; k < n; k += gridDim.x) {
+        const uint64_t s = first[1 + k];
+        const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
+        bool ok = nb64 < (1ull << 31);
+        uint64_t total = 0;
+        if (ok) {
+            const uint32_t nb = (uint32_t)nb64;
+            const KgEnd r = kg_stream<C>(stage, bm, A.in + A.in_off[s], nb, lim32, limit, [](uint32_t, uint32_t, uint64_t) {});
+            ok = kg_end_ok(r.st, r.end, nb);
+            total = r.st.total;
         }
-        if (!FILL && lane == 0) A.seg_idx[s] = (uint64_t)st.ncut + 1;
+        if (lane == 0) {
+            if (ok) {
+                A.out_size[s] = total;
+                if (A.status) A.status[s] = EZ_OK;
+                sized++;
+            } else {
+                const uint32_t at = atomicAdd(&ctr[2], 1u);
+                ctr[3 + at] = (uint32_t)s;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (blockIdx.x == 0) ctr[0] = (uint32_t)n;
+        if (sized) atomicAdd(&ctr[1], sized);
     }
 }
 
@@ -224,6 +286,21 @@ hipError_t launch_segments(const SegsArgs &a0, uint64_t max_len, void *workspace
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// The size query's slow area, 2 * count + 32 words: [the first list: count + 1][taken, sized][the second
+// list: 1 + count] ... [word 2 * count + 31: largest_slot's].
+uint32_t *size_segs_counters(uint32_t *slow, uint64_t count) { return slow + count + 1; }
+
+hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream_t st) {
+    uint32_t *ctr = size_segs_counters(a.slow, a.count);
+    const int chunk = size_chunk(max_len);
+    // (a block per listed stream; the list's length is on the device: the blocks past it leave at once)
+    const unsigned grid = (unsigned)(a.count < 8192 ? a.count : 8192);
+    if (chunk == 64) hipLaunchKernelGGL(k2g_size<64>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr);
+    else if (chunk == 1024) hipLaunchKernelGGL(k2g_size<1024>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr);
+    else hipLaunchKernelGGL(k2g_size<256>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr);
+    return hipGetLastError();
 }
 
 hipError_t launch_segments_merge(const uint64_t *out_off, uint64_t *out_size, int32_t *status, uint64_t count, const uint64_t *seg_idx,

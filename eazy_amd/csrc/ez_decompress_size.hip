@@ -13,8 +13,10 @@
 //            rule; the totals, the window and the flags are carried.
 // The next super-block starts at lane 63's true exit: a literal's body is never staged or read, however
 // long it is.  At the stream's end kz_end_ok decides: the wave writes out_size[s] and EZ_OK, or appends
-// the stream to the slow list, for the exact decoder run dry (ez_decompress.hip) -- every error, every
-// form k2_scan hands over, a MetaReset after output, a stream of 2 GiB or more.  Nothing else is written.
+// the stream to the slow list -- every error, every form k2_scan hands over, a MetaReset after output, a
+// stream of 2 GiB or more.  Nothing else is written.  The list goes to K2g's stage (k2g_size,
+// ez_decompress_segs.hip), which sizes the streams with MetaResets after output, and what that hands on
+// to the exact decoder run dry (ez_decompress.hip).
 #include <hip/hip_runtime.h>
 
 #include "ez_bytes.h"

@@ -234,7 +234,8 @@ DevCache &jump_cache();  // K2j's workspaces per (device, HIP stream)
 hipError_t batch_extents(const DecompressArgs &a, hipStream_t s, uint64_t *in_bytes, uint64_t *out_bytes);
 hipError_t launch_decompress_tok(const DecompressArgs &a, hipStream_t s);   // K2t, token-parallel wave per stream
 // K2z, the decoded-size query: the fast kernel (ez_decompress_size.hip; a.slow set, streams it cannot
-// take go there) and then the exact decoder run dry, or that one alone (a.slow == nullptr); max_len:
+// take go there), K2g's stage over that list (launch_size_segs) and then the exact decoder run dry over
+// the stage's list, or that one alone (a.slow == nullptr); max_len:
 // the caller's hint, the longest input stream (0 = unknown), which picks the fast kernel's chunk
 hipError_t launch_decompress_size(const DecompressArgs &a, uint64_t max_len, hipStream_t s);
 int size_chunk(uint64_t max_len);  // the wave kernel's chunk bytes for a hint
@@ -288,6 +289,13 @@ hipError_t launch_segments_merge(const uint64_t *out_off, uint64_t *out_size, in
 // count and block_size_limit.  (hipErrorOutOfMemory: the scratch could not be had)
 hipError_t launch_decompress_segmented(const DecompressArgs &a, hipStream_t s);
 DevCache &segs_cache();
+// K2g's stage of the size query (k2g_size, ez_decompress_segs.hip), behind K2z's kernels and before the
+// exact decoder: the streams of a.slow's list that K2g's walk can size (concatenated streams) get their
+// size and EZ_OK, the others go to a second list in the slow area's spare words.  size_segs_counters:
+// the stage's words there, which the launcher zeroes first: {entries taken from the first list, streams
+// sized, the second list: its length (the streams handed on), then its entries}
+uint32_t *size_segs_counters(uint32_t *slow, uint64_t count);
+hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream_t s);
 hipError_t segments_last(uint64_t counts[3]);  // of the last segmented decode: segments, handed over, query retries
 bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once, ez_k1_probe.hip)
 bool lds_mskor_in_lane_order();     // the LDS property k1_lean's one-atomic visit relies on (checked once)

@@ -17,7 +17,10 @@
 //              fails, or holds a form k2_scan hands over, stops the stream's walk: the cuts so far
 //              stand and the rest of the stream is the last segment, which the decoders see exactly
 //              as they see it today.
-// kg_serial is the whole chain by one walker, which tools/k2_segs_check.hip holds the chunked walk to.
+//   kg_end_ok  the size query's end step (k2g_size): a walk that went through, with a last segment that
+//              passes too, gives the stream's decoded length, the state's total.
+// kg_serial is the whole chain by one walker, which tools/k2_segs_check.hip and
+// tools/k2_segs_size_check.hip hold the chunked walk to.
 // All of them are functions over a byte pointer (the host check runs them over 64 emulated lanes).
 #pragma once
 
@@ -111,13 +114,21 @@ EZ_HD void kg_cuts(const KzWin &w, uint32_t sb, int lane, uint32_t nb, uint32_t 
     if (!st.stop && p != x) st.stop = true;  // (the fast step and k2_scan agree on every form k2_scan takes)
 }
 
+// The stream's end for the size query behind K2z (k2g_size, ez_decompress_segs.hip): the walk went
+// through without a stop, the chain ended at position end, and the last segment, the one since the
+// last cut, passes kz_end_ok's checks as every segment before it passed kg_seg_ok's.  Then the stream
+// decodes to st.total bytes with EZ_OK; else it is handed on.
+EZ_HD bool kg_end_ok(const KgState &st, uint32_t end, uint32_t nb) { return !st.stop && kz_end_ok(end, nb, st.total, st.bsl, st.maxd); }
+
 // The whole chain by one walker, in order: what the chunked walk computes, without the speculation.
-// at(p): the 16 bytes at stream position p (zeros past the stream's end).
+// at(p): the 16 bytes at stream position p (zeros past the stream's end); *end (optional): where the
+// chain ended.
 template <class At, class Cut>
-EZ_HD KgState kg_serial(At at, uint32_t nb, int32_t lim32, int64_t limit, Cut cut) {
+EZ_HD KgState kg_serial(At at, uint32_t nb, int32_t lim32, int64_t limit, Cut cut, uint32_t *end = nullptr) {
     KgState st = kg_start();
     uint32_t p = 0;
     while (p < nb && !st.stop) p = kg_step(at(p), p, nb, lim32, limit, st, cut);
+    if (end) *end = p;
     return st;
 }
 

@@ -408,3 +408,133 @@ func DecompressBatchSegmented(streams [][]byte, caps []uint64, blockSizeLimit in
 	}
 	return res, errs, nil
 }
+
+// DecompressBatchSized decodes independent streams whose decoded lengths the caller does not know, on
+// the GPU: ez_decompressed_size_batch sizes them, the sizes and the count of concatenated streams
+// that K2g's walk sized behind the fast kernels (ez_decompressed_size_segs_last) come back, the slots
+// are laid out from the sizes (each rounded up to 16 bytes), and the decode is
+// ez_decompress_batch_segmented's where that count is not zero, so that the segments of such streams
+// take the fast decoders too, else ez_decompress_batch's with the largest slot and the extents as its
+// hints.  The result for streams[k] is what NewReaderBytes(streams[k]) read to EOF produces, with
+// the Reader's error in errs[k].  The streams are staged into device memory and the calls run on the
+// null stream; every HIP call's result is checked before anything is used.
+func DecompressBatchSized(streams [][]byte, blockSizeLimit int) ([][]byte, []error, error) {
+	count := len(streams)
+	if count == 0 {
+		return nil, nil, nil
+	}
+	inOff := make([]uint64, count+1)
+	maxLen := 0
+	for k, s := range streams {
+		inOff[k+1] = inOff[k] + uint64(len(s))
+		if len(s) > maxLen {
+			maxLen = len(s)
+		}
+	}
+	host := make([]byte, 0, inOff[count])
+	for _, s := range streams {
+		host = append(host, s...)
+	}
+	var dIn, dOut, dInOff, dOutOff, dSize, dStatus, dWork unsafe.Pointer
+	defer func() {
+		for _, p := range []unsafe.Pointer{dIn, dOut, dInOff, dOutOff, dSize, dStatus, dWork} {
+			if p != nil {
+				C.hipFree(p)
+			}
+		}
+	}()
+	// every HIP call's result is checked: a failed copy must never hand back stale bytes as success
+	hip := func(r C.hipError_t) error {
+		if r != C.hipSuccess {
+			return ErrDevice
+		}
+		return nil
+	}
+	for _, a := range []struct {
+		p *unsafe.Pointer
+		n uint64
+	}{{&dIn, inOff[count]}, {&dInOff, 8 * uint64(count+1)}, {&dOutOff, 8 * uint64(count+1)}, {&dSize, 8 * uint64(count)},
+		{&dStatus, 4 * uint64(count)}, {&dWork, uint64(C.ez_decompress_workspace(C.uint64_t(count)))}} {
+		if err := hip(C.hipMalloc(a.p, C.size_t(a.n+16))); err != nil {
+			return nil, nil, err
+		}
+	}
+	if len(host) > 0 {
+		if err := hip(C.hipMemcpy(dIn, unsafe.Pointer(&host[0]), C.size_t(len(host)), C.hipMemcpyHostToDevice)); err != nil {
+			return nil, nil, err
+		}
+	}
+	if err := hip(C.hipMemcpy(dInOff, unsafe.Pointer(&inOff[0]), C.size_t(8*(count+1)), C.hipMemcpyHostToDevice)); err != nil {
+		return nil, nil, err
+	}
+	b := C.ez_batch{
+		in: (*C.uint8_t)(dIn), in_off: (*C.uint64_t)(dInOff), out_size: (*C.uint64_t)(dSize), status: (*C.int32_t)(dStatus),
+		count: C.uint64_t(count), max_len: C.uint64_t(maxLen),
+	}
+	if st := C.ez_decompressed_size_batch(C.int64_t(blockSizeLimit), &b, dWork, nil); st != C.EZ_OK {
+		return nil, nil, toErr(st, 0)
+	}
+	size := make([]uint64, count)
+	// (hipMemcpy to host waits for the query's kernels on the null stream, and reports their faults)
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&size[0]), dSize, C.size_t(8*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, err
+	}
+	var counts [3]uint64
+	if st := C.ez_decompressed_size_segs_last(dWork, C.uint64_t(count), (*C.uint64_t)(unsafe.Pointer(&counts[0]))); st != C.EZ_OK {
+		return nil, nil, toErr(st, 0)
+	}
+	outOff := make([]uint64, count+1)
+	largest := uint64(0)
+	for k := range streams {
+		slot := (size[k] + 15) &^ 15
+		outOff[k+1] = outOff[k] + slot
+		if slot > largest {
+			largest = slot
+		}
+	}
+	if err := hip(C.hipMalloc(&dOut, C.size_t(outOff[count]+16))); err != nil {
+		return nil, nil, err
+	}
+	if err := hip(C.hipMemcpy(dOutOff, unsafe.Pointer(&outOff[0]), C.size_t(8*(count+1)), C.hipMemcpyHostToDevice)); err != nil {
+		return nil, nil, err
+	}
+	b.out = (*C.uint8_t)(dOut)
+	b.out_off = (*C.uint64_t)(dOutOff)
+	b.max_len = C.uint64_t(largest) // (decode: the largest output slot)
+	b.in_bytes = C.uint64_t(inOff[count])
+	b.out_bytes = C.uint64_t(outOff[count])
+	var st C.int
+	if counts[1] != 0 {
+		st = C.ez_decompress_batch_segmented(C.int64_t(blockSizeLimit), &b, nil, nil)
+	} else {
+		st = C.ez_decompress_batch(C.int64_t(blockSizeLimit), &b, dWork, nil)
+	}
+	if st != C.EZ_OK {
+		return nil, nil, toErr(st, 0)
+	}
+	out := make([]byte, outOff[count]+1)
+	status := make([]int32, count)
+	if outOff[count] > 0 {
+		if err := hip(C.hipMemcpy(unsafe.Pointer(&out[0]), dOut, C.size_t(outOff[count]), C.hipMemcpyDeviceToHost)); err != nil {
+			return nil, nil, err
+		}
+	}
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&size[0]), dSize, C.size_t(8*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, err
+	}
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&status[0]), dStatus, C.size_t(4*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, err
+	}
+	res := make([][]byte, count)
+	errs := make([]error, count)
+	for k := range streams {
+		if size[k] > outOff[k+1]-outOff[k] {
+			return nil, nil, ErrDevice // (never: a size is at most its slot)
+		}
+		res[k] = out[outOff[k] : outOff[k]+size[k] : outOff[k]+size[k]]
+		if status[k] != 0 {
+			errs[k] = toErr(C.int(status[k]), 0)
+		}
+	}
+	return res, errs, nil
+}

@@ -312,6 +312,19 @@ int ez_select_size_route(int kind);
  * spans are in neither); all 0 where the parts route did not run or found in_bytes too small.  The
  * caller has synchronised that call's stream; the call reads the counters back from the device. */
 int ez_decompressed_size_parts_last(uint64_t counts[3]);
+/* Concatenated streams in the size query (a MetaReset after output, see K2g below): the fast kernels
+ * hand such a stream over, and a stage behind them walks every handed-over stream as
+ * ez_stream_segments_batch does, a wave per stream, keeping the total instead of the cuts.  A stream
+ * whose walk ends at its input's end with every segment passing the fast decoders' checks gets
+ * out_size[s] = the total and EZ_OK there; every other one goes on to the exact decoder run dry.  The
+ * stage keeps three counters in the workspace, which this call reads back: counts[0] = streams the fast
+ * kernels handed over, counts[1] = those the stage sized, counts[2] = those it handed on to the exact
+ * decoder (counts[0] = counts[1] + counts[2]).  workspace and count are those of an
+ * ez_decompressed_size_batch call with a workspace whose stream the caller has synchronised; count ==
+ * 0 gives zeros.  EZ_EINVAL for a NULL workspace or counts.  A caller that decodes next takes
+ * ez_decompress_batch_segmented where counts[1] != 0, so that the decode leaves the exact decoder too.
+ * Held by tests/test_k2_segs_size.py and tests/test_gpu_size_segments.py. */
+int ez_decompressed_size_segs_last(const void *workspace, uint64_t count, uint64_t counts[3]);
 
 /* K2g: concatenated streams.  A stream may hold a MetaReset after output (reader.go:305-311, 327-344: a
  * Writer that was Reset, or streams joined back to back); ez_decompress_batch hands such a stream to

@@ -7,7 +7,7 @@ median [p10 - p90]).  Log data (eazy_amd/synth.py) in frames of 64 KiB, compress
     s1024x16   1,024 streams of 16 segments
     s64x64     64 streams of 64 segments
 
-    python tools/segments_bench.py [--shapes s4096x4,s1024x16,s64x64] [--rounds 15] [--out FILE]
+    python tools/segments_bench.py [--shapes s4096x4,s1024x16,s64x64] [--rounds 15] [--out FILE] [--sized]
 
 Per shape, alternating in one loop after a warm-up:
     batch      decompress_batch with a workspace and every hint: each stream holds a Reset after output,
@@ -20,6 +20,12 @@ and bytes are checked against the data, the query's arrays against the frames' o
 segmented call's counters (segments, none handed over).  One JSON line per shape: medians in ms, the
 10th and 90th percentiles as the run-to-run spread, the query's share of the segmented call, the
 segmented call over the floor, and whether the segmented call's p90 lies below the batch call's p10.
+--sized measures the caller who knows no decoded lengths instead, two legs on the joined streams:
+    sizes         decompressed_sizes with a workspace and the longest stream as its hint;
+    sized_decode  decompress_batch_sized (the query, one read-back, the decode).
+Their sizes, statuses and bytes are checked, and where the library has the size query's K2g stage
+its counters (every stream taken and sized, none handed on) and the segmented decode behind it.  The
+mode runs on a build without that stage too, for the comparison.
 Needs a GPU; there is no fallback."""
 
 import argparse
@@ -42,6 +48,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--window-ms", type=float, default=20.0)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--sized", action="store_true", help="measure decompressed_sizes and decompress_batch_sized instead")
     args = ap.parse_args()
 
     import numpy as np
@@ -107,9 +114,31 @@ def main():
             ez.decompress_batch(packed, poff, off, out=out, sizes=sz["f"], status=st["f"], workspace=ws, max_len=FRAME, in_bytes=in_bytes,
                                 out_bytes=frames * FRAME)
 
+        def sizes():
+            ez.decompressed_sizes(packed, joff, sizes=sz["j"], status=st["j"], workspace=ws, max_len=max_in)
+
+        def sized_decode():
+            return ez.decompress_batch_sized(packed, joff)
+
         legs = {"batch": batch, "query": query, "segmented": segmented, "floor": floor}
         kernels, last = {}, None
-        for k, fn in legs.items():  # results first
+        if args.sized:
+            legs = {"sizes": sizes, "sized_decode": sized_decode}
+            stage = getattr(ez, "decompressed_size_segs_last", None)  # (None: a build without the stage)
+            sizes()
+            torch.cuda.synchronize()
+            assert sz["j"].cpu().tolist() == [segs * FRAME] * count and int(st["j"].abs().sum()) == 0, name
+            counters = list(stage(ws, count)) if stage else None
+            assert counters in (None, [count, count, 0]), (name, counters)
+            o, oo, osz, ost = sized_decode()
+            torch.cuda.synchronize()
+            assert osz.cpu().tolist() == [segs * FRAME] * count and int(ost.abs().sum()) == 0, name
+            assert torch.equal(oo, jooff) and torch.equal(o[: frames * FRAME], data), name
+            last = ez.segments_last() if stage else (0, 0, 0)
+            assert not stage or last[:2] == (frames, 0), (name, last)
+            kernels = {"sized_decode": ez.decompress_kernel_last(), "stage_counters": counters}
+            del o
+        for k, fn in ({} if args.sized else legs).items():  # results first
             out.zero_()
             fn()
             torch.cuda.synchronize()
@@ -145,10 +174,11 @@ def main():
             v = np.array(v)
             res[k] = {"median_ms": round(float(np.median(v)), 4), "p10_ms": round(float(np.percentile(v, 10)), 4),
                       "p90_ms": round(float(np.percentile(v, 90)), 4), "calls_per_window": inner[k]}
-        res["query_share_of_segmented"] = round(res["query"]["median_ms"] / res["segmented"]["median_ms"], 4)
-        res["segmented_over_floor"] = round(res["segmented"]["median_ms"] / res["floor"]["median_ms"], 4)
-        res["batch_over_segmented"] = round(res["batch"]["median_ms"] / res["segmented"]["median_ms"], 4)
-        res["segmented_below_batch"] = res["segmented"]["p90_ms"] < res["batch"]["p10_ms"]
+        if not args.sized:
+            res["query_share_of_segmented"] = round(res["query"]["median_ms"] / res["segmented"]["median_ms"], 4)
+            res["segmented_over_floor"] = round(res["segmented"]["median_ms"] / res["floor"]["median_ms"], 4)
+            res["batch_over_segmented"] = round(res["batch"]["median_ms"] / res["segmented"]["median_ms"], 4)
+            res["segmented_below_batch"] = res["segmented"]["p90_ms"] < res["batch"]["p10_ms"]
         line = json.dumps(res)
         print(line, flush=True)
         if args.out:
