@@ -12,8 +12,10 @@
 //    extra insert of i+1 (writer.go:315-318) is the accepting lane's own second store, after
 //    the visited lanes' one (LDS stores of one wave land in issue order), hashed from its
 //    own bytes x+1 .. x+4;
-//  * only saturated counts (24 forward / 8 backward with room left) take the cooperative
-//    extension (gext), as a rare branch.
+//  * only counts at their cap (24 or 40 forward / 8 backward) take the cooperative extension
+//    (gext), as a rare branch, which also finds whether the match has room past the cap;
+//  * while every group of the wave is far enough from its stream's end, the window runs in an
+//    interior form without end clamps, liveness terms and record-room test (lean_run).
 // Loads of the lean parse carry no bounds logic: every stream the loop reads has 64 readable bytes
 // before it and 64 after it (k1_lean copies the few streams at the batch's edges into padded
 // slots first), so each piece is one plain aligned load (LeanIn, ez_k1_device.h).
@@ -22,6 +24,7 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace ez {
@@ -165,7 +168,10 @@ __device__ __forceinline__ void bytes48(const LeanIn &L, const uint8_t *p, int32
 }
 
 #if (EZ_EXP & 65536)
-__device__ unsigned long long g_lean_hist[18];
+// [0..17] windows by acceptor lane (0: none); [18], [19] acceptors whose capped count had / had not room
+// left; [20] wave iterations that took the gext branch, [21] wave iterations, [22] those in which an
+// acceptor had room left (the branch's condition before the limits moved into it)
+__device__ unsigned long long g_lean_hist[23];
 #endif
 
 // k1_lean's parse of fresh single-Write streams, G lanes (a group) per stream, 64 / G groups per
@@ -251,29 +257,30 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
     budget += (int64_t)(4 * A.max_len + 64) * S;
 
     V16 w0{0, 0}, w1{0, 0}, w2{0, 0};  // bytes x-8 .. x+7, x+8 .. x+23 (and x+24 .. x+39) of this lane's x
-    for (;;) {
-        // groups whose stream ended: its size word
-        if (__builtin_amdgcn_ballot_w64(!live && pending) != 0) {
-            if (!live && pending) {
-                if (lj == 0) A.out_size[s] = (uint64_t)nrec | ((uint64_t)err << 48);
-                pending = false;
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(live) == 0) break;
-        if (budget < 0) {
-            if (live) err = EZ_ESTUCK;
-            live = false;
-            continue;
-        }
-        // the parse, until one of the groups' streams ends (the bookkeeping above stays out of it)
-        const uint64_t lm = __builtin_amdgcn_ballot_w64(live);
-        do {
+
+    // A group is interior while its stream is live, its record area has room for a record and
+    // i + kIn <= n.  A window at i judges x = i .. i+G-1; with i + G - 1 + CAP <= n, for every lane:
+    //  * n - 3 - i >= G: all G positions are visits (nvalid = G, valid);
+    //  * n - x >= CAP: the forward count (<= CAP) ends inside the stream, and so does the zero
+    //    run's (its candidate is below x: n - cand > CAP, and cand + 8 < n);
+    //  * x + 1 + 4 <= n: a window match makes its i+1 insert;
+    //  * the window's bytes end at x + CAP - 1 < n.
+    // So the interior window has no end clamp, no liveness term and no record-room test; the exact
+    // limits of a saturated count are gext's, in both forms of the window.  (The counts alone
+    // would bear a bound one byte looser, since a count that reaches CAP goes to gext, which holds
+    // it to the stream's end; the bound here is the one at which no lane needs that.)
+    constexpr int32_t kIn = G + CAP - 1;
+
+    // One window of every group of the wave.  IN: every group is interior (above); else the
+    // general window, which also serves ending streams, dead groups and a full record area.
+    auto window = [&](auto in_tag) __attribute__((always_inline)) {
+        constexpr bool IN = decltype(in_tag)::value;
         budget--;
         if constexpr (W40) wr.bytes48(i, g, lj, w0, w1, w2);
         else wr.bytes(i, g, lj, w0, w1);
-        const int32_t nvalid = n - 3 - i < G ? n - 3 - i : G;
+        const int32_t nvalid = IN ? G : (n - 3 - i < G ? n - 3 - i : G);
         const int32_t x = i + lj;
-        const bool valid = live && lj < nvalid;
+        const bool valid = IN || (live && lj < nvalid);
 
         // ---- visit (writer.go:213-217): hash, and in one LDS atomic the table's entry or the
         // nearest earlier lane with the same hash, and this lane's position into the table
@@ -294,51 +301,54 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
         const bool rl = cand >= done && cand < x;
         const uint64_t e0 = w0.hi ^ c0.hi, e1 = w1.lo ^ c1.lo, e2 = w1.hi ^ c1.hi;
         int32_t jf = W40 ? first_diff40(e0, e1, e2, w2.lo ^ c2.lo, w2.hi ^ c2.hi) : first_diff24(e0, e1, e2);
-        jf = jf < n - x ? jf : n - x;
+        if constexpr (!IN) jf = jf < n - x ? jf : n - x;
         int32_t bl = x - done;
         if (rl) bl = bl < cand ? bl : cand;
         int32_t jb = last_diff8(w0.lo ^ c0.lo);
         jb = jb < bl ? jb : bl;
-        const bool zr = rl && c0.hi == 0 && cand + 8 < n;
+        const bool zr = rl && c0.hi == 0 && (IN || cand + 8 < n);
         const int32_t fw = rl ? jf : (jf < done - cand ? jf : done - cand);
         const bool acc = valid && (zr || fw + jb >= kMinCopyChunk);
 
-        // ---- this lane's action if it is the group's first acceptor
+        // ---- this lane's action if it is the group's first acceptor.  ext: a count that reached
+        // its cap (bit 0 forward, bit 1 backward); whether the match has room to go on past the
+        // cap is gext's to find, from its exact limits
         int32_t lit, nx, dist, ext;
         bool force = false;
         if (zr) {  // writeZeros :407-439
             int32_t zf = W40 ? first_diff40(0, c1.lo, c1.hi, c2.lo, c2.hi) : first_diff24(0, c1.lo, c1.hi);
-            zf = zf < n - cand ? zf : n - cand;
+            if constexpr (!IN) zf = zf < n - cand ? zf : n - cand;
             int32_t zb = last_diff8(c0.lo);
             zb = zb < cand - done ? zb : cand - done;
             lit = cand - zb;
             nx = cand + zf;
             dist = 0;
-            ext = (zf == CAP && n - cand > CAP ? 1 : 0) | (zb == 8 && cand - done > 8 ? 2 : 0);
+            ext = (zf == CAP ? 1 : 0) | (zb == 8 ? 2 : 0);
         } else {  // writeRunlen :441-489 / window match :303-321
             lit = x - jb;
             nx = x + fw;
             dist = x - cand;
             force = rl;
-            ext = (jf == CAP && (rl ? n - x : (done - cand < n - x ? done - cand : n - x)) > CAP ? 1 : 0) |
-                  (jb == 8 && bl > 8 ? 2 : 0);
+            ext = (jf == CAP ? 1 : 0) | (jb == 8 ? 2 : 0);
         }
         const uint64_t am64 = __builtin_amdgcn_ballot_w64(acc);
         const uint32_t am = (uint32_t)(am64 >> (G * g)) & kGMask;
         const int a = am ? __builtin_ctz(am) : -1;
 #if (EZ_EXP & 65536)
-        if (live && lj == 0) atomicAdd(&g_lean_hist[a + 1], 1ull);  // (experiment builds: the acceptor lane, -1 none)
+        if ((IN || live) && lj == 0) atomicAdd(&g_lean_hist[a + 1], 1ull);  // (experiment builds: the acceptor lane, -1 none)
+        if (lj == 0 && g == 0) atomicAdd(&g_lean_hist[21], 1ull);
 #endif
-        const bool act = live && a >= 0;
-        // the group's next position, whether the acceptor needs an exact extension, and whether it
-        // makes the i+1 insert (a window match, writer.go:315-318)
-        const bool ins1 = !rl && !zr && x + 1 + 4 <= n;
+        const bool act = (IN || live) && a >= 0;
+        // the group's next position, whether the acceptor's counts reached their caps, and whether
+        // it makes the i+1 insert (a window match, writer.go:315-318)
+        const bool ins1 = !rl && !zr && (IN || x + 1 + 4 <= n);
         const int32_t pack = nx | (ext << 28) | ((int32_t)ins1 << 30);
         // (one ds_bpermute from each group's first acceptor: fewer VALU than four v_readlane + selects)
         const int32_t sel = __builtin_amdgcn_ds_bpermute(4 * (G * g + (a < 0 ? 0 : a)), pack);
         int32_t nxt = sel & 0x0fffffff;
         if (__builtin_amdgcn_ballot_w64(act && ((sel >> 28) & 3) != 0) != 0) {
-            // rare: a saturated count; exact lengths by the whole group (as k1_parse)
+            // rare: a count at its cap; exact lengths by the whole group (as k1_parse).  A count
+            // with no room past its cap (flim <= CAP, blim <= 8) comes back from gext as it was.
             // the acceptor's candidate, capped backward count (<= 8) and branch
             const int32_t info = cand | (((zr ? cand : x) - lit) << 16) | ((int32_t)rl << 29) | ((int32_t)zr << 30);
             const int32_t ib = bcast(info, G * g + (a < 0 ? 0 : a));
@@ -352,6 +362,11 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
             const int32_t blim = zra ? ca - done : (rla ? ((xa - done) < ca ? (xa - done) : ca) : xa - done);
             const int32_t flim = zra ? n - ca : (rla ? n - xa : ((done - ca) < n - xa ? done - ca : n - xa));
             int32_t fx, cx;
+#if (EZ_EXP & 65536)
+            if (need && lj == 0) atomicAdd(&g_lean_hist[18 + ((e & 1 && flim > CAP) || (e & 2 && blim > 8) ? 0 : 1)], 1ull);
+            if (lj == 0 && g == 0) atomicAdd(&g_lean_hist[20], 1ull);
+            if (__builtin_amdgcn_ballot_w64(need && ((e & 1 && flim > CAP) || (e & 2 && blim > 8))) != 0 && lj == 0 && g == 0) atomicAdd(&g_lean_hist[22], 1ull);
+#endif
             gext<G, GWU>(GWU{p}, need && (e & 1), need && (e & 2), g, lj, fa, ca, mode, done, CAP, flim, blim, fx, cx);
             if (need) {
                 const int32_t f = (e & 1) ? fx : (sel & 0x0fffffff) - fa;
@@ -381,18 +396,56 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
         const bool st_rec = act && lj == a;
         const uint64_t rv = rec_pack(lit, nx - lit, dist, force);
         const uint32_t rat = (uint32_t)nrec;
-        const bool rec_room = (uint32_t)nrec < rcap32;
+        const bool rec_room = IN || (uint32_t)nrec < rcap32;
         if (act) {
             if (!rec_room) { err = EZ_ESTUCK; live = false; }
             nrec++;
             i = done = nxt;
-        } else if (live) {
+        } else if (IN || live) {
             i += nvalid;
         }
-        if (live && (err || i + 4 > n)) live = false;
-        wr.advance(p, i, lj, live);  // the next window's region
+        // (an interior group that reaches its stream's end is marked when the interior loop ends)
+        if constexpr (!IN) {
+            if (live && (err || i + 4 > n)) live = false;
+        }
+        wr.advance(p, i, lj, IN || live);  // the next window's region (up to the stream's end: in bounds)
         __builtin_amdgcn_sched_barrier(0);
         if (st_rec && rec_room) __builtin_nontemporal_store(rv, rec + rat);
+    };
+
+    for (;;) {
+        // groups whose stream ended: its size word
+        if (__builtin_amdgcn_ballot_w64(!live && pending) != 0) {
+            if (!live && pending) {
+                if (lj == 0) A.out_size[s] = (uint64_t)nrec | ((uint64_t)err << 48);
+                pending = false;
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(live) == 0) break;
+        if (budget < 0) {
+            if (live) err = EZ_ESTUCK;
+            live = false;
+            continue;
+        }
+        // the interior loop, while every group of the wave is interior: the test is made before
+        // every window, so the window itself needs none.  It counts the budget down and leaves the
+        // test of it to this outer loop: every window advances its group's i or, where a match
+        // ends at i itself, done up to i (done <= i <= n), so the loop ends within 2n windows
+        // whatever the budget says, and a wrong parse still cannot hang the grid.
+        if (__builtin_amdgcn_ballot_w64(live && i + kIn <= n && (uint32_t)nrec < rcap32) == ~0ull) {
+            do {
+                window(std::true_type{});
+            } while (__builtin_amdgcn_ballot_w64(i + kIn <= n && (uint32_t)nrec < rcap32) == ~0ull);
+            // a match that ran to the stream's end; the group that left the interior has its next
+            // window in the general loop below
+            if (i + 4 > n) live = false;
+            continue;
+        }
+        // the general loop, until one of the groups' streams ends (the bookkeeping above stays out
+        // of it): a group leaves the interior for good, so the wave does not return to it
+        const uint64_t lm = __builtin_amdgcn_ballot_w64(live);
+        do {
+            window(std::false_type{});
         } while (__builtin_amdgcn_ballot_w64(live) == lm && budget >= 0);
     }
 }
@@ -489,7 +542,7 @@ void lean_report_timeline(uint64_t blocks, hipStream_t st) {
 #if (EZ_EXP & 65536)
 // (experiment builds) the acceptor-lane histogram of the launch before
 void lean_report_hist(hipStream_t st) {
-    unsigned long long hst[18];
+    unsigned long long hst[23];
     (void)hipStreamSynchronize(st);
     (void)hipMemcpyFromSymbol(hst, HIP_SYMBOL(g_lean_hist), sizeof hst);
     unsigned long long tot = 0, vis = 0;
@@ -498,7 +551,9 @@ void lean_report_hist(hipStream_t st) {
     vis += hst[0] * 16ull;
     fprintf(stderr, "lean windows %llu (no accept %llu); visited lanes %.3f of 16; by acceptor lane:", tot, hst[0], (double)vis / (double)tot);
     for (int t = 1; t < 17; t++) fprintf(stderr, " %.3f", (double)hst[t] / (double)tot);
-    fprintf(stderr, "\n");
+    fprintf(stderr, "\nlean capped counts: %llu acceptors with room left, %llu without; gext branch in %llu of %llu wave iterations (%.2f %%), %llu with room left (%.2f %%)\n",
+            hst[18], hst[19], hst[20], hst[21], 100.0 * (double)hst[20] / (double)(hst[21] ? hst[21] : 1), hst[22],
+            100.0 * (double)hst[22] / (double)(hst[21] ? hst[21] : 1));
     memset(hst, 0, sizeof hst);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lean_hist), hst, sizeof hst);
 }
