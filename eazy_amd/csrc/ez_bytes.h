@@ -94,5 +94,21 @@ EZ_HD void put_small(uint8_t *d, V16 v, uint32_t k) {
     if (k & 1) d[o] = (uint8_t)x;
 }
 
+// the last k in [0, n) with key(k) <= x, for keys that do not decrease and key(0) <= x (0 for n <= 1):
+// the stream of a chunk or a part from the exclusive scan of the counts, the record of an output byte
+template <class I, class Key, class X>
+EZ_HD I last_le_by(I n, Key key, X x) {
+    I lo = 0, hi = n;  // key(lo) <= x < key(hi)
+    while (hi - lo > 1) {
+        const I m = (lo + hi) >> 1;
+        if (key(m) <= x) lo = m;
+        else hi = m;
+    }
+    return lo;
+}
+template <class T, class I>
+EZ_HD I last_le(const T *a, I n, T x) {
+    return last_le_by(n, [a](I m) { return a[m]; }, x);
+}
 
 }  // namespace ez

@@ -50,63 +50,12 @@
 // (kj_guarded).  Over-stated hints only make the workspace larger; one hint alone counts as none.
 #include <hip/hip_runtime.h>
 
-#include "ez_bytes.h"
 #include "ez_cache.h"
-#include "ez_internal.h"
-#include "ez_k2_parse.h"
+#include "ez_k2_jump.h"
+#include "ez_wave.h"
 
 namespace ez {
 namespace {
-
-constexpr int32_t kJC = 1024;                        // compressed bytes per chunk at most (JWork.jc: 1,024 or 256)
-constexpr int32_t kJW = kJC / 32;                    // bitmap words per chunk
-constexpr uint32_t kJGap = 0xffffffffu;              // ptr: not a byte of any stream's output
-constexpr uint32_t kJZero = 0xfffffffeu;             // ptr: a zero byte of the history before the stream
-constexpr uint32_t kJCopy = 0x80000000u;             // JTok.kd: a copy (distance in the low bits; 0: zero region)
-constexpr int kJPasses = 34;                         // pointer-jumping passes at most (chains up to 2^34)
-constexpr uint32_t kJRec = kJC / 2 + 2;              // token records of a chunk at most (a token takes >= 2 bytes)
-
-struct JHead {
-    uint32_t chunk0, nchunk;  // the stream's chunks
-    uint32_t state;           // 0: K2j decodes it; 1: handed over
-    int32_t bsl;              // log2 of the window (MetaReset)
-    uint64_t total;           // output bytes
-    uint64_t ntok;            // token records
-    uint64_t tok0;            // its first record
-    // (c_on) where the chain stops: the input consumed by whole tokens, and a literal starting there
-    // whose body runs past the input (its header length, its length; 0: none)
-    int32_t tstop, tj;
-    int64_t tL;
-};
-
-// the ptr array's first byte: out_off[0] less the continuation's history, rounded down to 16 bytes
-__device__ __forceinline__ uint64_t jg0(const DecompressArgs &A) {
-    return (A.out_off[0] - (A.c_on ? A.c_hist : 0)) & ~15ull;
-}
-
-struct JTok {
-    uint32_t dst, L, kd, src;  // output position, length, kJCopy | distance (or 0: literal), literal's input position
-};
-
-struct JWork {
-    JHead *head;
-    uint32_t *cbase;    // count+1: first chunk of each stream (and the total)
-    uint32_t *entry, *sexit, *bits;
-    uint32_t *cnt;      // tokens of a chunk's true chain
-    uint64_t *cout;     // output bytes of a chunk
-    uint32_t *cflag;    // kJF* bits, bits 8-15: the chunk's last MetaReset
-    uint64_t *ctbase, *cobase;
-    JTok *tok;
-    uint64_t tok_cap;
-    JTok *ltok;         // kj_tok's records, chunk-local (kJRec per chunk, dst from the chunk's output start)
-    uint32_t *cmaxd;    // the longest copy distance of a chunk
-    uint32_t *ptr;
-    uint32_t *pass;     // [kJPasses]: the pass changed something; [kJPasses]: the guard (kj_init); then token records allocated
-    int32_t jc;         // compressed bytes per chunk (jchunk)
-    // the input and output extents the workspace was sized from (the caller's hints, or read back):
-    // kj_init checks the real offsets against them
-    uint64_t in_ext, out_ext;
-};
 
 // The guard: the batch's real extents exceed the ones its workspace was sized from (an under-stated
 // ez_batch.in_bytes / out_bytes).  kj_init sets it; every later kernel but kj_final returns at once,
@@ -114,54 +63,15 @@ struct JWork {
 // exact decoder.
 __device__ __forceinline__ bool kj_guarded(const JWork &W) { return W.pass[kJPasses] != 0; }
 
-// Chunks of 256 bytes for batches of at most 96 KiB of input (a Reader's refill of ~64 KiB: four
-// times the lanes, each walk a quarter as long -- one wave of 1 KiB chunks was the refill's critical
-// path: 0.60 -> 0.51 ms; C++ NewReader over 64 KiB pieces 143 -> 200 - 208 MiB/s), 1 KiB above (at
-// 122 / 244 KiB, 256-byte chunks measured 0.85 / 1.03 against 0.82 / 0.66 ms: the per-stream scan and
-// fix over four times the chunks outweigh the shorter walks)
-inline int32_t jchunk(uint64_t in_total) { return in_total <= (96ull << 10) ? 256 : kJC; }
-
-enum : uint32_t { kJFBad = 1, kJFReset = 2, kJFOutFirst = 4, kJFResetLate = 8, kJFBreak = 16 };
-
-// the stream of chunk c (binary search over cbase)
-__device__ __forceinline__ uint32_t chunk_stream(const uint32_t *cbase, uint32_t count, uint32_t c) {
-    uint32_t lo = 0, hi = count;  // cbase[lo] <= c < cbase[hi]
-    while (hi - lo > 1) {
-        const uint32_t m = (lo + hi) >> 1;
-        if (cbase[m] <= c) lo = m;
-        else hi = m;
-    }
-    return lo;
-}
-
-// the 16 input bytes at p of a stream at b (bytes past the batch read 0)
-__device__ __forceinline__ V16 jbytes(const uint8_t *b, int32_t p, const uint8_t *lo, const uint8_t *hi) {
-    const uint8_t *y = b + p;
-    return y + 16 <= hi ? ld16v(y) : ld_clamped(y, lo, hi);
-}
-
-// input bytes the token (or padding run, or meta) at p takes; -1 for a form to hand over (a walk
-// that goes on steps 1 byte)
-__device__ __forceinline__ int32_t jadv(const uint8_t *b, int32_t p, int32_t nb, int32_t lim32, int64_t limit, const uint8_t *lo,
-                                        const uint8_t *hi, K2Tok &t, int &r) {
-    r = k2_scan(jbytes(b, p, lo, hi), p, nb, lim32, limit, t);
-    return r == kParseHandOver ? -1 : t.adv;
-}
-
 // The walks of kj_spec / kj_verify / kj_tok read their chunk's tokens from LDS: a block's 64 chunks are
 // consecutive in the batch's input (a stream's chunks follow each other, and so do the streams), so
 // the block stages the bytes from its first chunk's start to 16 past its last chunk's end with
 // coalesced 16-byte loads, and every token step is then an LDS read instead of a dependent global
-// load (a 61 KiB stream: the three walks 840 -> see DESIGN §4 K2j).
-// kj_spec starts each chunk's speculative parse kJWarm bytes before it (positions before the chunk are
-// not recorded), so that its chain has usually met the true one by the chunk's start: kj_verify's
-// walks then end at their first step and kj_fix has (almost) nothing to redo
-constexpr int32_t kJWarm = 256;
-constexpr int32_t kJStage = 64 * kJC + kJWarm + 32;  // LDS bytes of a block's staged input
+// load (DESIGN §4 K2j has the times).  The walks themselves are ez_k2_jump.h's, over JStage as the accessor.
 struct JStage {
     uint8_t *lds;
     uint64_t base;  // batch offset of lds[0]
-    __device__ __forceinline__ V16 at(uint64_t y) const {  // 16 bytes at batch offset y (staged)
+    __device__ __forceinline__ V16 operator()(uint64_t y) const {  // 16 bytes at batch offset y (staged)
         const uint8_t *q = lds + (y - base);
         typedef uint64_t __attribute__((aligned(1))) u64u;
         return V16{*(const u64u *)q, *(const u64u *)(q + 8)};
@@ -181,11 +91,11 @@ __device__ __forceinline__ JStage kj_stage(const DecompressArgs &A, bool live, u
         atomicMax((unsigned long long *)&ext[1], (unsigned long long)end);
     }
     __syncthreads();
-    const uint64_t base = ext[0], stop = ext[1] + 16, total = A.in_off[A.count];
+    const uint64_t base = ext[0], stop = ext[1] + 16;
+    const KjBatch in{A.in, A.in_off[A.count]};
     if (base < stop) {
         for (uint64_t o = (uint64_t)threadIdx.x * 16; base + o < stop; o += (uint64_t)blockDim.x * 16) {
-            const uint64_t y = base + o;
-            const V16 v = y + 16 <= total ? ld16v(A.in + y) : ld_clamped(A.in + y, A.in, A.in + total);
+            const V16 v = in(base + o);
             typedef uint64_t __attribute__((aligned(8))) u64a;
             *(u64a *)(lds + o) = v.lo;
             *(u64a *)(lds + o + 8) = v.hi;
@@ -194,15 +104,6 @@ __device__ __forceinline__ JStage kj_stage(const DecompressArgs &A, bool live, u
     __syncthreads();
     return JStage{lds, base};
 }
-// jadv on staged bytes (the token at stream position p; b0 = the stream's batch offset)
-__device__ __forceinline__ int32_t jadv_s(const JStage &S, uint64_t b0, int32_t p, int32_t nb, int32_t lim32, int64_t limit, K2Tok &t,
-                                          int &r, bool partial = false) {
-    r = k2_scan(S.at(b0 + (uint64_t)p), p, nb, lim32, limit, t, partial);
-    return r == kParseHandOver ? -1 : t.adv;
-}
-
-// (jadv_fast, the speculative walks' step: ez_k2_parse.h)
-
 // ---- 0: chunks per stream
 __global__ __launch_bounds__(1024) void kj_init(DecompressArgs A, JWork W) {
     __shared__ uint32_t part[1024];
@@ -260,24 +161,11 @@ __global__ __launch_bounds__(64) void kj_spec(DecompressArgs A, JWork W) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[kJStage];
     if (kj_guarded(W)) return;
     const uint32_t lane = threadIdx.x;
-    const uint32_t total = W.cbase[A.count];
     const uint32_t c = blockIdx.x * 64 + lane;
-    bool live = c < total;
-    const uint32_t s = live ? chunk_stream(W.cbase, (uint32_t)A.count, c) : 0;
-    live = live && !W.head[s].state;
-    const uint64_t b0 = A.in_off[s];
-    const int32_t nb = (int32_t)(A.in_off[s + 1] - A.in_off[s]);
-    const int32_t c0 = (int32_t)(c - W.cbase[s]) * W.jc, ce = c0 + W.jc < nb ? c0 + W.jc : nb;
-    const int32_t w0 = c0 > kJWarm ? c0 - kJWarm : 0;
-    const JStage S = kj_stage(A, live, b0 + (uint64_t)w0, b0 + (uint64_t)ce, stage);
-    if (!live) return;
-    for (int k = 0; k < kJW; k++) bm[lane][k] = 0;
-    int32_t p = w0;
-    while (p < c0) p += jadv_fast(S.at(b0 + (uint64_t)p));  // (the warm-up: nothing recorded)
-    while (p < ce) {
-        bm[lane][(p - c0) >> 5] |= 1u << ((p - c0) & 31);
-        p += jadv_fast(S.at(b0 + (uint64_t)p));
-    }
+    const KjChunk K = kj_chunk(c, W.cbase, (uint32_t)A.count, A.in_off, W.head, W.jc);
+    const JStage S = kj_stage(A, K.live, K.b0 + (uint64_t)kj_warm0(K.c0), K.b0 + (uint64_t)K.ce, stage);
+    if (!K.live) return;
+    const int32_t p = kj_spec_walk(S, K.b0, K.c0, K.ce, bm[lane]);
     uint32_t *g = W.bits + (uint64_t)c * kJW;
     for (int k = 0; k < kJW; k++) g[k] = bm[lane][k];
     W.sexit[c] = (uint32_t)p;
@@ -290,52 +178,17 @@ __global__ __launch_bounds__(64) void kj_spec(DecompressArgs A, JWork W) {
 // speculative parse visited -- its speculative exit is then its true exit -- or its end), and a wave
 // per stream then redoes, in order, only the chunks whose predecessor did not merge (kj_fix).
 // texit[c]: chunk c's true exit given that entry; entry[c]: the entry the check assumed
-__device__ __forceinline__ int32_t kj_walk_true(const JWork &W, uint32_t cg, const uint8_t *b, int32_t a, int32_t cs, int32_t ce,
-                                                const uint8_t *lo, const uint8_t *hi) {
-    const uint32_t *g = W.bits + (uint64_t)cg * kJW;
-    int32_t q = a;
-    while (q < ce) {
-        if ((g[(q - cs) >> 5] >> ((q - cs) & 31)) & 1u) return (int32_t)W.sexit[cg];  // merged: its exit is the chain's
-        q += jadv_fast(jbytes(b, q, lo, hi));
-    }
-    return q;
-}
-
 __global__ __launch_bounds__(64) void kj_verify(DecompressArgs A, JWork W) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[kJStage];
     if (kj_guarded(W)) return;
-    const uint32_t total = W.cbase[A.count];
     const uint32_t c = blockIdx.x * 64 + threadIdx.x;
-    bool live = c < total;
-    const uint32_t s = live ? chunk_stream(W.cbase, (uint32_t)A.count, c) : 0;
-    live = live && !W.head[s].state;
-    const uint64_t b0 = A.in_off[s];
-    const int32_t nb = (int32_t)(A.in_off[s + 1] - A.in_off[s]);
-    const uint32_t k = c - W.cbase[s];
-    const int32_t c0 = (int32_t)k * W.jc, ce = c0 + W.jc < nb ? c0 + W.jc : nb;
-    const JStage S = kj_stage(A, live, b0 + (uint64_t)c0, b0 + (uint64_t)ce, stage);
-    if (!live) return;
-    const int32_t a = k == 0 ? 0 : (int32_t)W.sexit[c - 1];
-    int32_t x;
-    if (k == 0) {
-        x = (int32_t)W.sexit[c];  // (chunk 0's speculation starts at the stream's start: it is the true chain)
-    } else if (a >= ce) {
-        x = a;  // an entry past the chunk (inside a long token) passes through
-    } else {
-        const uint32_t *g = W.bits + (uint64_t)c * kJW;
-        int32_t q = a < c0 ? c0 : a;  // (a < c0 cannot happen: a speculative exit is >= its chunk's end)
-        x = -1;
-        while (q < ce) {
-            if ((g[(q - c0) >> 5] >> ((q - c0) & 31)) & 1u) {
-                x = (int32_t)W.sexit[c];
-                break;
-            }
-            q += jadv_fast(S.at(b0 + (uint64_t)q));
-        }
-        if (x < 0) x = q;
-    }
+    const KjChunk K = kj_chunk(c, W.cbase, (uint32_t)A.count, A.in_off, W.head, W.jc);
+    const JStage S = kj_stage(A, K.live, K.b0 + (uint64_t)K.c0, K.b0 + (uint64_t)K.ce, stage);
+    if (!K.live) return;
+    const int32_t a = K.c0 == 0 ? 0 : (int32_t)W.sexit[c - 1];  // (chunk 0 starts at the stream's start, on the true chain)
     W.entry[c] = (uint32_t)a;
-    W.cnt[c] = (uint32_t)x;  // (the true exit; kj_tok overwrites cnt with the token count)
+    // (the true exit; kj_tok overwrites cnt with the token count)
+    W.cnt[c] = (uint32_t)kj_follow(S, K.b0, a, K.c0, K.ce, W.bits + (uint64_t)c * kJW, W.sexit + c);
 }
 
 __global__ __launch_bounds__(64) void kj_fix(DecompressArgs A, JWork W) {
@@ -343,7 +196,6 @@ __global__ __launch_bounds__(64) void kj_fix(DecompressArgs A, JWork W) {
     const uint32_t s = blockIdx.x, lane = threadIdx.x;
     JHead &H = W.head[s];
     if (H.state) return;
-    const uint8_t *b = A.in + A.in_off[s], *lo = A.in, *hi = A.in + A.in_off[A.count];
     const int32_t nb = (int32_t)(A.in_off[s + 1] - A.in_off[s]);
     const uint32_t c00 = H.chunk0, nch = H.nchunk;
     uint32_t *texit = W.cnt;
@@ -366,25 +218,22 @@ __global__ __launch_bounds__(64) void kj_fix(DecompressArgs A, JWork W) {
         }
         const uint32_t jf = k + (uint32_t)__builtin_ctzll(m);  // the first chunk entered wrongly
         const int32_t e = jf - 1 == fx_at ? fx_val : (int32_t)texit[c00 + jf - 1];  // its true entry
-        // an entry past chunk jf (inside a long token): no token starts in the chunks it covers
-        uint32_t kw = jf;
-        if (e >= nb || e >= (int32_t)(jf + 1) * W.jc) {
-            kw = e >= nb ? nch : (uint32_t)(e / W.jc);
-            for (uint32_t x = jf + lane; x < kw; x += 64) {
-                W.entry[c00 + x] = (uint32_t)e;
-                texit[c00 + x] = (uint32_t)e;
-            }
-            if (kw >= nch) {
-                fx_at = nch - 1;
-                fx_val = e;
-                break;
-            }
+        // the chunks before the one that holds e pass it through
+        const uint32_t kw = kj_holder(e, jf, nb, nch, W.jc);
+        for (uint32_t x = jf + lane; x < kw; x += 64) {
+            W.entry[c00 + x] = (uint32_t)e;
+            texit[c00 + x] = (uint32_t)e;
         }
-        // chunk kw holds e: the true chain from there (one lane; rare)
+        if (kw >= nch) {
+            fx_at = nch - 1;
+            fx_val = e;
+            break;
+        }
+        // chunk kw holds e: the true chain from there (one lane; rare), on global memory
         int32_t x = 0;
         if (lane == 0) {
             const int32_t cs = (int32_t)kw * W.jc, ce = cs + W.jc < nb ? cs + W.jc : nb;
-            x = kj_walk_true(W, c00 + kw, b, e, cs, ce, lo, hi);
+            x = kj_follow(KjBatch{A.in, A.in_off[A.count]}, A.in_off[s], e, cs, ce, W.bits + (uint64_t)(c00 + kw) * kJW, W.sexit + c00 + kw);
             W.entry[c00 + kw] = (uint32_t)e;
             texit[c00 + kw] = (uint32_t)x;
         }
@@ -392,10 +241,8 @@ __global__ __launch_bounds__(64) void kj_fix(DecompressArgs A, JWork W) {
         fx_val = __shfl(x, 0);
         k = kw + 1;
     }
-    // the chain must end exactly at the stream's end (else the last token runs past the input; a
-    // Reader's read-ahead, c_on, stops before that token: kj_tok finds it)
     const int32_t last = nch - 1 == fx_at ? fx_val : (int32_t)texit[c00 + nch - 1];
-    if (lane == 0 && (A.c_on ? last < nb : last != nb)) H.state = 1;
+    if (lane == 0 && kj_chain_bad(last, nb, A.c_on != 0)) H.state = 1;
 }
 
 // ---- 2a: the true chain of each chunk, parsed once: tokens, output bytes, forms and metas, a record
@@ -404,58 +251,20 @@ __global__ __launch_bounds__(64) void kj_fix(DecompressArgs A, JWork W) {
 __global__ __launch_bounds__(64) void kj_tok(DecompressArgs A, JWork W) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[kJStage];
     if (kj_guarded(W)) return;
-    const uint32_t total = W.cbase[A.count];
     const uint32_t c = blockIdx.x * 64 + threadIdx.x;
-    bool live = c < total;
-    const uint32_t s = live ? chunk_stream(W.cbase, (uint32_t)A.count, c) : 0;
-    live = live && !W.head[s].state;
-    const uint64_t b0 = A.in_off[s];
-    const int32_t nb = (int32_t)(A.in_off[s + 1] - A.in_off[s]);
-    const int32_t c0 = (int32_t)(c - W.cbase[s]) * W.jc, ce = c0 + W.jc < nb ? c0 + W.jc : nb;
-    const JStage S = kj_stage(A, live, b0 + (uint64_t)c0, b0 + (uint64_t)ce, stage);
-    if (!live) return;
-    const int64_t limit = A.block_size_limit;
-    const int32_t lim32 = k2_lim32(limit);
-    int32_t p = (int32_t)W.entry[c];
-    uint32_t n = 0, fl = 0, maxd = 0;
-    uint64_t out = 0;
-    const bool partial = A.c_on != 0;
-    JTok *rec = W.ltok + (uint64_t)c * kJRec;
-    while (p < ce) {
-        K2Tok t;
-        int r;
-        const int32_t ad = jadv_s(S, b0, p, nb, lim32, limit, t, r, partial);
-        if (ad < 0 || (r == kParseToken && n >= kJRec)) {
-            fl |= kJFBad;
-            break;
-        }
-        if (r == kScanTail) {  // the chain stops here (one chunk of the stream meets it)
-            JHead &H = W.head[s];
-            H.tstop = p;
-            H.tj = t.adv ? t.j : 0;
-            H.tL = t.adv ? t.L : 0;
-            break;
-        }
-        if (r == kScanReset) {
-            fl |= (out ? kJFResetLate : 0) | kJFReset | (n == 0 ? 0 : kJFOutFirst);
-            fl = (fl & 0xffu) | (t.marg << 8);
-        } else if (r == kParseToken) {
-            rec[n++] = JTok{(uint32_t)out, (uint32_t)t.L, t.cp ? (kJCopy | t.D) : 0u, (uint32_t)(p + t.j)};
-            maxd = t.cp && t.D > maxd ? t.D : maxd;
-            out += (uint64_t)t.L;
-        } else if (r == kParseSkip && A.breaks) {  // (one-stream batches) a Break: (chunk, local position)
-            const V16 h = S.at(b0 + (uint64_t)p);
-            if (((uint32_t)h.lo & 0xffffu) == (0x80u | ((kMetaBreak | kMetaLen0) << 8))) {
-                const uint64_t at = atomicAdd((unsigned long long *)A.breaks, 1ull);
-                if (at < A.breaks_cap) A.breaks[1 + at] = ((uint64_t)c << 32) | (out & 0xffffffffull);
-            }
-        }
-        p += ad;
-    }
-    W.cnt[c] = n;
-    W.cout[c] = out;
-    W.cflag[c] = fl;
-    W.cmaxd[c] = maxd;
+    const KjChunk K = kj_chunk(c, W.cbase, (uint32_t)A.count, A.in_off, W.head, W.jc);
+    const JStage S = kj_stage(A, K.live, K.b0 + (uint64_t)K.c0, K.b0 + (uint64_t)K.ce, stage);
+    if (!K.live) return;
+    const auto brk = [&](uint64_t out) {  // (one-stream batches) a Break: (chunk, local position)
+        const uint64_t at = atomicAdd((unsigned long long *)A.breaks, 1ull);
+        if (at < A.breaks_cap) A.breaks[1 + at] = ((uint64_t)c << 32) | (out & 0xffffffffull);
+    };
+    const KjSum r = kj_tok_walk(S, K.b0, K.nb, K.ce, (int32_t)W.entry[c], k2_lim32(A.block_size_limit), A.block_size_limit, A.c_on != 0,
+                                W.ltok + (uint64_t)c * kJRec, W.head[K.s], A.breaks != nullptr, brk);
+    W.cnt[c] = r.n;
+    W.cout[c] = r.out;
+    W.cflag[c] = r.fl;
+    W.cmaxd[c] = r.maxd;
 }
 
 // ---- 2b: token and output positions of the chunks; the stream's checks (wave per stream)
@@ -474,44 +283,25 @@ __global__ __launch_bounds__(64) void kj_scan(DecompressArgs A, JWork W, uint64_
         const bool mine = j < nch;
         const uint64_t n = mine ? W.cnt[c00 + j] : 0, o = mine ? W.cout[c00 + j] : 0;
         const uint32_t fl = mine ? W.cflag[c00 + j] : 0;
-        uint32_t md = mine ? W.cmaxd[c00 + j] : 0;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) md = max(md, (uint32_t)__shfl_xor((int)md, d, 64));
-        maxd = max(maxd, md);
-        uint64_t in = n, io = o;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t vn = __shfl_up(in, d, 64), vo = __shfl_up(io, d, 64);
-            if ((int)lane >= d) {
-                in += vn;
-                io += vo;
-            }
-        }
+        maxd = max(maxd, wmax_u32(mine ? W.cmaxd[c00 + j] : 0));
+        const uint64_t in = wscan_add_u64(n), io = wscan_add_u64(o);
         const uint64_t obefore = ocarry + io - o;
         if (mine) {
             W.ctbase[c00 + j] = tcarry + in - n;
             W.cobase[c00 + j] = obefore;
         }
-        // a MetaReset only before any output (and the window it sets is the last such one)
-        const bool rbad = mine && (fl & kJFReset) && (obefore != 0 || (fl & (kJFOutFirst | kJFResetLate)) || (A.c_on && A.c_pos0 != 0));
-        if (__ballot(rbad || (mine && (fl & kJFBad)))) bad = true;
+        // (the window a stream's MetaResets set is the last one's)
+        if (__ballot(mine && kj_chunk_bad(fl, obefore, A.c_on && A.c_pos0 != 0))) bad = true;
         const uint64_t rm = __ballot(mine && (fl & kJFReset));
         if (rm) bsl = (int32_t)((__shfl(fl, 63 - __builtin_clzll(rm)) >> 8) & 0xff);
         tcarry = __shfl(tcarry + in, 63);
         ocarry = __shfl(ocarry + io, 63);
     }
     if (lane != 0) return;
-    const uint64_t cap = A.out_off[s + 1] - A.out_off[s];
-    // a literal at the input's end (c_on) whose body runs past it: the bytes there are are output too
-    const int32_t nb = (int32_t)(A.in_off[s + 1] - A.in_off[s]);
-    const uint64_t tail = A.c_on && H.tj > 0 ? (uint64_t)min((int64_t)H.tL, (int64_t)(nb - H.tstop - H.tj)) : 0;
-    // "missed meta": a token (or a literal's header) before the window is set
-    if (!bad && (ocarry > 0 || (A.c_on && H.tj > 0)) && bsl < 0) bad = true;
-    // ErrOverflow (reader.go:256-258): a distance past the window -- the exact decoder reports it
-    if (!bad && bsl >= 0 && bsl < 30 && maxd > (1u << bsl)) bad = true;
-    if (!bad && ocarry + tail > cap) {
-        bad = true;
-        if (A.end_state) A.end_state[0] = -2;  // (a caller that sizes its slot grows it and retries)
+    if (!bad) {
+        bool nospace;
+        bad = kj_stream_bad(ocarry, bsl, maxd, A.out_off[s + 1] - A.out_off[s], A.c_on != 0, H, (int32_t)(A.in_off[s + 1] - A.in_off[s]), nospace);
+        if (nospace && A.end_state) A.end_state[0] = -2;  // (a caller that sizes its slot grows it and retries)
     }
     if (!bad) {
         const uint64_t t0 = atomicAdd((unsigned long long *)tok_alloc, (unsigned long long)tcarry);
@@ -529,7 +319,7 @@ __global__ __launch_bounds__(64) void kj_place(DecompressArgs A, JWork W) {
     if (kj_guarded(W)) return;
     const uint32_t c = blockIdx.x;
     if (c >= W.cbase[A.count]) return;
-    const uint32_t s = chunk_stream(W.cbase, (uint32_t)A.count, c);
+    const uint32_t s = last_le(W.cbase, (uint32_t)A.count, c);
     const JHead &H = W.head[s];
     if (H.state) return;
     const JTok *src = W.ltok + (uint64_t)c * kJRec;
@@ -543,75 +333,15 @@ __global__ __launch_bounds__(64) void kj_place(DecompressArgs A, JWork W) {
 }
 
 // ---- 3: literal and zero bytes, and a pointer for every copied byte (thread per 16 output bytes)
-// output bytes [q, q + n) of stream s (n <= 16, inside its output): bytes into by, pointers into pt.
-// Pointers and the ptr array count from g0 = out_off[0] rounded down to 16 bytes: a batch may be a view
-// into a larger one (absolute offsets), whose bytes before out_off[0] are never touched.
-__device__ __forceinline__ void kj_piece(const DecompressArgs &A, const JWork &W, const JHead &H, uint32_t s, uint64_t q, uint32_t n,
-                                         uint64_t g0, uint32_t *by, uint32_t *pt) {
-    const uint64_t base = A.out_off[s];
-    const uint32_t hb = A.c_on ? (uint32_t)A.c_hist : 0u;  // history bytes before the output (a copy may read them)
-    const uint32_t p0 = (uint32_t)(q - base);
-    // the token holding p0: the last record with dst <= p0; the next ones by walking on
-    const JTok *tk = W.tok + H.tok0;
-    uint64_t a = 0, z = H.ntok;
-    while (z - a > 1) {
-        const uint64_t m = (a + z) >> 1;
-        if (tk[m].dst <= p0) a = m;
-        else z = m;
-    }
-    JTok t = tk[a];
-    uint32_t nxt = a + 1 < H.ntok ? tk[a + 1].dst : 0xffffffffu;
-    const uint8_t *in = A.in + A.in_off[s];
-    if (n == 16 && p0 + 16 <= t.dst + t.L) {  // the 16 bytes inside one token (long literals, runs, zeros)
-        const uint32_t x = (uint32_t)(base + p0 - g0);
-        if (t.kd == 0) {
-            const uint8_t *y = in + t.src + (p0 - t.dst);
-            const V16 v = y + 16 <= A.in + A.in_off[A.count] ? ld16v(y) : ld_clamped(y, A.in, A.in + A.in_off[A.count]);
-            by[0] = (uint32_t)v.lo, by[1] = (uint32_t)(v.lo >> 32), by[2] = (uint32_t)v.hi, by[3] = (uint32_t)(v.hi >> 32);
-            for (uint32_t k = 0; k < 16; k++) pt[k] = x + k;
-        } else if (t.kd == kJCopy) {
-            for (uint32_t k = 0; k < 16; k++) pt[k] = x + k;
-        } else {
-            const uint32_t D = t.kd & ~kJCopy;
-            for (uint32_t k = 0; k < 16; k++) pt[k] = p0 + k + hb >= D ? x + k - D : kJZero;
-        }
-        return;
-    }
-    for (uint32_t k = 0; k < n; k++) {
-        const uint32_t p = p0 + k;
-        while (p >= nxt) {
-            a++;
-            t = tk[a];
-            nxt = a + 1 < H.ntok ? tk[a + 1].dst : 0xffffffffu;
-        }
-        const uint32_t x = (uint32_t)(base + p - g0);
-        uint32_t v = 0;
-        if (t.kd == 0) {  // literal
-            v = in[t.src + (p - t.dst)];
-            pt[k] = x;
-        } else if (t.kd == kJCopy) {  // zero region
-            pt[k] = x;
-        } else {
-            const uint32_t D = t.kd & ~kJCopy;
-            pt[k] = p + hb >= D ? x - D : kJZero;
-        }
-        by[k >> 2] |= v << (8 * (k & 3));
-    }
-}
-
+// (kj_piece, ez_k2_jump.h: the bytes and pointers of up to 16 output bytes of one stream)
 __global__ __launch_bounds__(256) void kj_expand(DecompressArgs A, JWork W) {
     if (kj_guarded(W)) return;
     const uint64_t ob = A.out_off[0], g0 = jg0(A), end = A.out_off[A.count];
     const uint64_t hst = A.c_on ? ob - A.c_hist : ob;  // (c_on) the history [hst, ob): final bytes, pointing at themselves
     for (uint64_t g = g0 + ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; g < end; g += (uint64_t)gridDim.x * blockDim.x * 16) {
-        // the stream of the piece's first byte of the batch (binary search over the slots)
+        // the stream of the piece's first byte of the batch
         const uint64_t x0 = g > ob ? g : ob;
-        uint32_t s = 0, hs = (uint32_t)A.count;
-        while (hs - s > 1) {
-            const uint32_t m = (s + hs) >> 1;
-            if (A.out_off[m] <= x0) s = m;
-            else hs = m;
-        }
+        uint32_t s = last_le(A.out_off, (uint32_t)A.count, x0);
         const uint64_t ge = g + 16 < end ? g + 16 : end;
         const JHead H = W.head[s];
         if (!H.state && A.out_off[s] <= g && A.out_off[s] + H.total >= g + 16 && ge == g + 16) {
@@ -724,29 +454,6 @@ __global__ __launch_bounds__(256) void kj_final(DecompressArgs A, JWork W) {
     }
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the workspace layout of a batch (in_total / out_total: the end offsets in_off[count], out_off[count])
-struct JLayout {
-    uint64_t chunks, tok_cap;
-    size_t o_head, o_cbase, o_entry, o_sexit, o_bits, o_cnt, o_cout, o_cflag, o_ctb, o_cob, o_tok, o_ltok, o_maxd, o_ptr, o_pass, total;
-    JLayout(uint64_t count, uint64_t in_total, uint64_t out_total) {
-        chunks = in_total / (uint64_t)jchunk(in_total) + 2 * count + 2;
-        tok_cap = in_total / 2 + chunks + 16;  // (a token takes >= 2 input bytes; one may start in each chunk's last byte)
-        size_t off = 0;
-        auto take = [&](size_t n) {
-            const size_t o = off;
-            off += al256(n);
-            return o;
-        };
-        o_head = take(sizeof(JHead) * count), o_cbase = take(4 * (count + 1)), o_entry = take(4 * chunks), o_sexit = take(4 * chunks),
-        o_bits = take(4 * kJW * chunks), o_cnt = take(4 * chunks), o_cout = take(8 * chunks), o_cflag = take(4 * chunks),
-        o_ctb = take(8 * chunks), o_cob = take(8 * chunks), o_tok = take(sizeof(JTok) * tok_cap),
-        o_ltok = take(sizeof(JTok) * kJRec * chunks), o_maxd = take(4 * chunks), o_ptr = take(4 * out_total + 16),
-        o_pass = take(8 * (kJPasses + 2));
-        total = off;
-    }
-};
 }  // namespace
 
 // K2j's workspaces per (device, HIP stream) (ez_cache.h)
@@ -790,10 +497,6 @@ hipError_t launch_decompress_jump(const DecompressArgs &a, hipStream_t st) {
     if (e != hipSuccess) return e;
     const uint64_t out_total = out_bytes + (a.c_on ? a.c_hist : 0) + 16;  // (+ the history a continuation reads)
     const JLayout Y(a.count, in_total, out_total);
-    const uint64_t chunks = Y.chunks, tok_cap = Y.tok_cap;
-    const size_t o_head = Y.o_head, o_cbase = Y.o_cbase, o_entry = Y.o_entry, o_sexit = Y.o_sexit, o_bits = Y.o_bits, o_cnt = Y.o_cnt,
-                 o_cout = Y.o_cout, o_cflag = Y.o_cflag, o_ctb = Y.o_ctb, o_cob = Y.o_cob, o_tok = Y.o_tok, o_ptr = Y.o_ptr,
-                 o_pass = Y.o_pass;
     // the caller's workspace when it gives one large enough, else this (device, stream)'s (its lease
     // is held through the launches: another host thread growing it meanwhile would free it under them)
     CacheLease lease;
@@ -805,37 +508,18 @@ hipError_t launch_decompress_jump(const DecompressArgs &a, hipStream_t st) {
         if (!lease->ensure(Y.total)) return hipErrorOutOfMemory;  // (the caller decodes the batch on K2t)
         w = (uint8_t *)lease->p;
     }
-    JWork W{};
-    W.head = (JHead *)(w + o_head);
-    W.cbase = (uint32_t *)(w + o_cbase);
-    W.entry = (uint32_t *)(w + o_entry);
-    W.sexit = (uint32_t *)(w + o_sexit);
-    W.bits = (uint32_t *)(w + o_bits);
-    W.cnt = (uint32_t *)(w + o_cnt);
-    W.cout = (uint64_t *)(w + o_cout);
-    W.cflag = (uint32_t *)(w + o_cflag);
-    W.ctbase = (uint64_t *)(w + o_ctb);
-    W.cobase = (uint64_t *)(w + o_cob);
-    W.tok = (JTok *)(w + o_tok);
-    W.tok_cap = tok_cap;
-    W.ltok = (JTok *)(w + Y.o_ltok);
-    W.cmaxd = (uint32_t *)(w + Y.o_maxd);
-    W.ptr = (uint32_t *)(w + o_ptr);
-    W.pass = (uint32_t *)(w + o_pass);
-    W.jc = jchunk(in_total);
-    W.in_ext = in_total;
-    W.out_ext = out_bytes;
+    const JWork W = Y.bind(w, in_total, out_bytes);
     uint64_t *tok_alloc = (uint64_t *)(W.pass + kJPasses + 2);
     if ((e = hipMemsetAsync(W.pass, 0, 8 * (kJPasses + 2), st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.ptr, 0xff, 4 * out_total + 16, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(kj_init, dim3(1), dim3(1024), 0, st, a, W);
-    const unsigned cgrid = (unsigned)((chunks + 63) / 64);
+    const unsigned cgrid = (unsigned)((Y.chunks + 63) / 64);
     hipLaunchKernelGGL(kj_spec, dim3(cgrid), dim3(64), 0, st, a, W);
     hipLaunchKernelGGL(kj_verify, dim3(cgrid), dim3(64), 0, st, a, W);
     hipLaunchKernelGGL(kj_fix, dim3((unsigned)a.count), dim3(64), 0, st, a, W);
     hipLaunchKernelGGL(kj_tok, dim3(cgrid), dim3(64), 0, st, a, W);
     hipLaunchKernelGGL(kj_scan, dim3((unsigned)a.count), dim3(64), 0, st, a, W, tok_alloc);
-    hipLaunchKernelGGL(kj_place, dim3((unsigned)chunks), dim3(64), 0, st, a, W);
+    hipLaunchKernelGGL(kj_place, dim3((unsigned)Y.chunks), dim3(64), 0, st, a, W);
     const uint64_t pieces = (out_total + 15) / 16;  // (out_total: the batch's output and the alignment slack)
     const unsigned egrid = (unsigned)(pieces / 256 + 1 < 8192 ? pieces / 256 + 1 : 8192);
     hipLaunchKernelGGL(kj_expand, dim3(egrid), dim3(256), 0, st, a, W);

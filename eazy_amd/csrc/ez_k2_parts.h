@@ -51,15 +51,7 @@ EZ_HD uint32_t kp_stage_base(uint32_t ps, uint32_t c) { return ps >= c ? ps - c 
 
 // the stream of part g of the batch: the last s < count with base[s] <= g (base: the exclusive scan of
 // the streams' part counts, count + 1 entries; streams without parts share their successor's base)
-EZ_HD uint64_t kp_stream_of(const uint32_t *base, uint64_t count, uint32_t g) {
-    uint64_t lo = 0, hi = count;
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) / 2;
-        if (base[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+EZ_HD uint64_t kp_stream_of(const uint32_t *base, uint64_t count, uint32_t g) { return last_le(base, count, g); }
 
 // a part's record: the first pass's result for the chain that enters at ent
 struct KpRec {
