@@ -220,6 +220,16 @@ def release_cached(device: int = -1) -> None:
     _check(_lib().ez_release_cached(device))
 
 
+def fill_cached(byte: int, device: int = -1) -> int:
+    """ez_fill_cached: set every idle buffer ez_release_cached would free to `byte` (0..255; -1:
+    touch nothing) and return the device and pinned bytes covered (device < 0: all).  Tests only."""
+    L = _lib()
+    L.ez_fill_cached.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+    n = C.c_uint64(0)
+    _check(L.ez_fill_cached(device, byte, C.byref(n)))
+    return int(n.value)
+
+
 def multi_last_shards() -> list:
     """ez_multi_last_shards: [(device, t0_ms, t1_ms)] of the last multi-device batch call's shards."""
     L = _lib()

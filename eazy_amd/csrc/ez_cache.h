@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <atomic>
 #include <map>
@@ -122,6 +123,24 @@ class DevCache {
                 ++it;
             }
         }
+    }
+    // set every idle entry of dev (all devices for dev < 0) to `byte`, device and pinned (byte < 0: count
+    // only), and add the bytes covered to *bytes; entries a call holds are skipped as trim() skips
+    // them.  Waits for the device (hipMemset); the caller is bound to dev.  (ez_fill_cached)
+    bool fill(int dev, int byte, uint64_t *bytes) {
+        std::lock_guard<std::mutex> g(m_);
+        bool ok = true;
+        for (auto &kv : map_) {
+            CacheEntry &e = *kv.second;
+            if ((dev >= 0 && kv.first.first != dev) || e.refs != 0 || !e.mu.try_lock()) continue;
+            if (byte >= 0) {
+                if (e.p && hipMemset(e.p, byte, e.cap) != hipSuccess) ok = false;
+                if (e.hp) memset(e.hp, byte, e.hcap);
+            }
+            *bytes += (e.p ? e.cap : 0) + (e.hp ? e.hcap : 0);
+            e.mu.unlock();
+        }
+        return ok;
     }
     size_t entries(int dev) {
         std::lock_guard<std::mutex> g(m_);

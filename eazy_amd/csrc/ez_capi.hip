@@ -410,3 +410,32 @@ extern "C" int ez_release_cached(int device) {
     multi_release_cached(device);
     return EZ_OK;
 }
+
+// Testing: sets the scratch ez_release_cached would free to `byte` (0..255; -1: touches nothing) and
+// reports its size in *bytes (may be NULL): the K1 / K1c scratch, K2j workspaces, the parts route's and
+// ez_decompress_batch_segmented's scratch per (device, HIP stream), ez_writer_write_many's staging
+// (device and pinned), the Reader handles' shared K2j workspace and the multi-device calls' pooled
+// shard buffers, on `device` (< 0: every device).  Scratch a call is using at that moment is skipped.
+// It waits for the device before it fills and before it returns.
+extern "C" int ez_fill_cached(int device, int byte, uint64_t *bytes) {
+    if (bytes) *bytes = 0;
+    const int have = device_count();
+    if (have <= 0) return EZ_EDEVICE;
+    if (device >= have || byte < -1 || byte > 255) return EZ_EINVAL;
+    DeviceGuard keep(-1);
+    uint64_t n = 0;
+    bool ok = true;
+    for (int d = device < 0 ? 0 : device; d < (device < 0 ? have : device + 1); d++) {
+        if (hipSetDevice(d) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return EZ_EDEVICE;
+        ok &= k1_cache().fill(d, byte, &n);
+        ok &= ez::jump_cache().fill(d, byte, &n);
+        ok &= ez::size_cache().fill(d, byte, &n);
+        ok &= ez::segs_cache().fill(d, byte, &n);
+        ok &= reader_fill_cached(d, byte, &n);
+        ok &= writer_fill_cached(d, byte, &n);
+        ok &= multi_fill_cached(d, byte, &n);
+        if (hipDeviceSynchronize() != hipSuccess) return EZ_EDEVICE;
+    }
+    if (bytes) *bytes = n;
+    return ok ? EZ_OK : EZ_EDEVICE;
+}

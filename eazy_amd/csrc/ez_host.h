@@ -17,6 +17,11 @@ int device_count();  // (ez_capi.hip; 0 when the runtime reports none)
 void reader_release_cached(int dev);    // the Readers' shared K2j workspace of dev, unless one is using it
 void multi_release_cached(int device);  // the idle shard buffers of device (< 0: every device)
 void writer_release_cached(int dev);    // ez_writer_write_many's idle staging, device buffers and records of dev
+// ez_fill_cached's part beside each: the same buffers set to `byte` (< 0: counted only), their bytes
+// added to *bytes; false when a hipMemset failed
+bool reader_fill_cached(int dev, int byte, uint64_t *bytes);
+bool multi_fill_cached(int device, int byte, uint64_t *bytes);
+bool writer_fill_cached(int dev, int byte, uint64_t *bytes);
 
 struct DeviceGuard {
     int prev = -1;

@@ -3,6 +3,7 @@
 // stream per shard, each running the single-device batch calls of ez_capi.hip.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -53,8 +54,9 @@ struct ShardRes {
     hipStream_t st = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the shard's device work
     DBuf in, in_off, out, out_off, size, status, ws, packed, packed_off;
+    std::array<DBuf *, 9> bufs() { return {&in, &in_off, &out, &out_off, &size, &status, &ws, &packed, &packed_off}; }
     void release_bufs() {
-        for (DBuf *b : {&in, &in_off, &out, &out_off, &size, &status, &ws, &packed, &packed_off}) b->release();
+        for (DBuf *b : bufs()) b->release();
     }
 };
 
@@ -94,6 +96,22 @@ class ShardPool {
             if (hipSetDevice(kv.first) != hipSuccess) continue;
             for (ShardRes *r : kv.second) r->release_bufs();
         }
+    }
+    // set the idle resources' buffers on dev to `byte` (< 0: count only); their bytes are added to *bytes
+    bool fill(int dev, int byte, uint64_t *bytes) {
+        std::lock_guard<std::mutex> lk(m_);
+        bool ok = true;
+        for (auto &kv : idle_) {
+            if (dev >= 0 && kv.first != dev) continue;
+            if (hipSetDevice(kv.first) != hipSuccess) continue;
+            for (ShardRes *r : kv.second)
+                for (DBuf *b : r->bufs()) {
+                    if (!b->p) continue;
+                    if (byte >= 0 && hipMemset(b->p, byte, b->cap) != hipSuccess) ok = false;
+                    *bytes += b->cap;
+                }
+        }
+        return ok;
     }
 
   private:
@@ -205,6 +223,7 @@ int each_shard(Shards &sh, F f, bool record = true) {
 }  // namespace
 
 void ez::multi_release_cached(int device) { shard_pool().trim(device); }
+bool ez::multi_fill_cached(int device, int byte, uint64_t *bytes) { return shard_pool().fill(device, byte, bytes); }
 
 // Introspection (tests, measurement): the shards of the last multi-device call and their device
 // intervals (ms from the earliest shard start on the same device; -1 if not measurable)

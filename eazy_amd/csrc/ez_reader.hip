@@ -505,6 +505,15 @@ void ez::reader_release_cached(int dev) {
     }
 }
 
+bool ez::reader_fill_cached(int dev, int byte, uint64_t *bytes) {
+    ReaderJws &J = reader_jws(dev);
+    if (!J.mu.try_lock()) return true;
+    const bool ok = !J.buf.p || byte < 0 || hipMemset(J.buf.p, byte, J.buf.cap) == hipSuccess;
+    *bytes += J.buf.p ? J.buf.cap : 0;
+    J.mu.unlock();
+    return ok;
+}
+
 // Input is uploaded in windows from b[i] on, not the whole of b per call: a Read loop over one large
 // NewReaderBytes buffer then moves each input byte to the device about once.  A window that ends inside
 // a token makes the decoder stop there with EZ_ESHORTBUF and nothing of that token consumed

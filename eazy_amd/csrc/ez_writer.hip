@@ -377,6 +377,7 @@ bool many_shares(const ez_writer *w, uint64_t n, ez::CompressArgs &a) {
 }  // namespace
 
 void ez::writer_release_cached(int dev) { many_cache().trim(dev); }
+bool ez::writer_fill_cached(int dev, int byte, uint64_t *bytes) { return many_cache().fill(dev, byte, bytes); }
 
 extern "C" int ez_writer_write(ez_writer *w, const uint8_t *p, size_t n, uint8_t *out, size_t cap, size_t *out_n) {
     *out_n = 0;

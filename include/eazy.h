@@ -251,7 +251,8 @@ int ez_compress_batch_writes(int64_t block, int64_t htable, int flags, const ez_
  * and packed_off[0 .. count] are written.  The source is read in whole aligned
  * dwords that hold a byte of a stream, so up to 3 bytes either side of it (never
  * outside a page the stream lies in; the bytes are read, not used).
- * count == 0 writes packed_off[0] only.  Held by tests/test_gpu_k3_pack.py. */
+ * count == 0 writes packed_off[0] only.  The workspace's contents on entry are ignored: it need
+ * not be cleared, and may hold what any earlier call left.  Held by tests/test_gpu_k3_pack.py. */
 size_t ez_pack_workspace(uint64_t count);
 int ez_pack_batch(const uint8_t *slots, const uint64_t *slot_off, const uint64_t *sizes, uint64_t count,
                   uint8_t *packed, uint64_t *packed_off, void *workspace, void *hip_stream);
@@ -269,7 +270,13 @@ int ez_pack_batch(const uint8_t *slots, const uint64_t *slot_off, const uint64_t
  * out_size[s] on untouched; a stream with an error may leave part of its slot overwritten (a fast
  * decoder's output before the hand-over), never a byte outside it.  A fast decoder takes only
  * slots of at least 16 bytes and batches of at least 16 input bytes; the others go to the exact
- * decoder.  Held by tests/test_gpu_k2r.py, test_gpu_k2t.py and test_gpu_k2j.py. */
+ * decoder.  Held by tests/test_gpu_k2r.py, test_gpu_k2t.py and test_gpu_k2j.py.
+ * The workspace's contents on entry are ignored: it need not be cleared, it may hold what any
+ * earlier call left there (this call's, the size query's, another batch's), and nothing is written
+ * past ez_decompress_workspace(count) bytes.  out_size[s] and status[s] are written for every
+ * stream of the batch, empty and refused ones included.  Scratch the library keeps between calls
+ * carries nothing from one call to the next (see ez_release_cached).  The same holds for
+ * ez_decompressed_size_batch and ez_decompress_batch_segmented. */
 size_t ez_decompress_workspace(uint64_t count);
 int ez_decompress_batch(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
 /* K2z: what ez_decompress_batch would report for every stream given a slot that is large enough,
@@ -353,6 +360,8 @@ int ez_decompressed_size_segs_last(const void *workspace, uint64_t count, uint64
  * Asynchronous on hip_stream; never waits for the stream.  Memory touched: reads in[0 .. in_off[count])
  * as ez_decompress_batch does, in_off and out_off; no output buffer is needed; writes only
  * seg_idx[0 .. count], seg_in and seg_out[0 .. seg_total[0]], seg_total[0 .. 1] and the workspace.
+ * The workspace's contents on entry are ignored: it need not be cleared, and nothing is written past
+ * ez_segments_workspace(count) bytes.
  * Held by tests/test_k2_segments.py and tests/test_gpu_segments.py. */
 size_t ez_segments_workspace(uint64_t count);
 int ez_stream_segments_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *seg_idx, uint64_t *seg_in, uint64_t *seg_out,
@@ -398,7 +407,9 @@ int ez_compress_batch_multi(int64_t block, int64_t htable, int flags, const uint
                             int32_t *status);
 /* Decompress: stream s = in[in_off[s] .. in_off[s+1]) read to EOF as NewReaderBytes does (Break
  * metas skipped) into out[out_off[s] .. out_off[s+1]); out_size[count] bytes produced,
- * status[count] (may be NULL) EZ_OK or the first error, as ez_decompress_batch. */
+ * status[count] (may be NULL) EZ_OK or the first error, as ez_decompress_batch.  On this host
+ * path the bytes of a slot past out_size[s] are unspecified (each shard's whole device range is
+ * copied down, whatever its pooled buffer held). */
 int ez_decompress_batch_multi(int64_t block_size_limit, const uint8_t *in, const uint64_t *in_off, uint64_t count,
                               const int *devices, int ndev, uint8_t *out, const uint64_t *out_off, uint64_t *out_size,
                               int32_t *status);
@@ -412,12 +423,26 @@ int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in
                                      const int *devices, int ndev, uint64_t *out_size, int32_t *status);
 
 /* Frees the device scratch kept between batch calls (no reference counterpart; a caching
- * allocator's empty_cache): K1 / K1c scratch and K2j workspaces per (device, HIP stream), the
- * multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace,
- * ez_decompress_batch_segmented's scratch; device < 0 =
- * every device.  Scratch in use by a concurrent call is kept.  Entries beyond 8 streams per device
- * are also freed least recently used first as new streams arrive. */
+ * allocator's empty_cache).  The set: per (device, HIP stream), the K1 / K1c / K1x scratch of
+ * ez_compress_batch and _writes, the K2j workspaces of ez_decompress_batch, the parts route's scratch
+ * of ez_decompressed_size_batch, ez_decompress_batch_segmented's scratch and ez_writer_write_many's
+ * staging (device and pinned); per device, the Reader handles' shared K2j workspace; and the
+ * multi-device calls' pooled shard buffers.  device < 0 = every device.  Scratch in use by a
+ * concurrent call is kept.  Entries beyond 8 streams per device are also freed least recently used
+ * first as new streams arrive.
+ * Scratch kept between calls carries nothing from one call to the next: every call gives the results
+ * it would give on freshly allocated scratch of any contents (held by tests/test_gpu_dirty_scratch.py
+ * and tests/test_gpu_call_order.py). */
 int ez_release_cached(int device);
+/* Testing / introspection: sets every idle buffer of the set ez_release_cached frees (the same
+ * set: the per-(device, HIP stream) scratch of K1 / K1c / K1x, K2j, the parts route,
+ * ez_decompress_batch_segmented and ez_writer_write_many, device and pinned; the Reader handles'
+ * shared K2j workspace; the multi-device calls' pooled shard buffers) to `byte` (0..255), or touches
+ * nothing and only counts with byte = -1; *bytes (may be NULL) gets the device and pinned bytes
+ * covered.  device < 0 = every device.  Scratch a concurrent call holds is skipped.  Waits for the
+ * device before it fills and before it returns.  EZ_EINVAL for any other byte or a device that does
+ * not exist. */
+int ez_fill_cached(int device, int byte, uint64_t *bytes);
 /* Introspection (tests, measurement): the shards of the last ez_*_batch_multi call in this process
  * (returns their number; up to cap entries filled, any pointer may be NULL): each shard's device and
  * its device interval (upload to download) in ms from the earliest shard start on that device. */

@@ -145,7 +145,7 @@ GUARD = 64  # bytes of 0xFF on both sides of the input view
 
 
 def _run(cuda, ins, jc=None, slots=None, handed="auto", hints=None, lead=5, kind="j", last=None, max_len=None,
-         block_size_limit=0, pad=0):
+         block_size_limit=0, pad=0, ws_init=0):
     """Decode ins with the decoder `kind` forced ("j", "r", "t"; "": the library's choice) and check
     everything the module's docstring lists.
     jc: the chunk size a K2j batch must take (asserted from its input).  slots: {index: slot bytes}
@@ -154,10 +154,15 @@ def _run(cuda, ins, jc=None, slots=None, handed="auto", hints=None, lead=5, kind
     that do not fit their slot; "all": every stream; None: not checked).  hints: f(in_bytes, out_bytes) -> kwargs.
     last: the decoder the batch must have taken (default: kind).  max_len: the hint (True: the largest slot).
     pad: bytes (0xFF) inside the input view before comp_off[0] and after comp_off[count]; the view
-    itself lies between two guards of 64 bytes of 0xFF."""
+    itself lies between two guards of 64 bytes of 0xFF.
+    ws_init: what the workspace holds when the call starts, a fill byte or a tensor to copy from (an
+    earlier call's workspace).  The workspace lies between two guards (tests/dirty.py), which must be
+    intact afterwards; the exact decoder alone must leave all of it as it was.
+    Returns (the workspace as the forced decoder left it, streams it handed over, literals it deferred)."""
     import torch
 
     import eazy_amd as ez
+    from dirty import guarded, guards_intact, k2_lists
 
     count = len(ins)
     total_in = sum(len(b) for b in ins)
@@ -182,7 +187,8 @@ def _run(cuda, ins, jc=None, slots=None, handed="auto", hints=None, lead=5, kind
         out = torch.full((int(ooff[-1]) + 64,), 0xA5, dtype=torch.uint8, device=cuda)
         sz = torch.full((count,), -7, dtype=torch.int64, device=cuda)
         st = torch.full((count,), -7, dtype=torch.int32, device=cuda)
-        ws = torch.zeros(ez._lib().ez_decompress_workspace(count), dtype=torch.uint8, device=cuda)
+        ws_whole, ws = guarded(cuda, ez._lib().ez_decompress_workspace(count), ws_init)
+        ws0 = ws.clone()
         ez.select_decompress_kernel("" if exact else kind)
         try:
             ez.decompress_batch(comp, d_coff, d_ooff, block_size_limit=lim, out=out, sizes=sz, status=st, workspace=ws,
@@ -191,8 +197,12 @@ def _run(cuda, ins, jc=None, slots=None, handed="auto", hints=None, lead=5, kind
             took = ez.decompress_kernel_last()
         finally:
             ez.select_decompress_kernel("")
+        guards_intact(ws_whole, "the exact decoder" if exact else "K2" + kind)
         if not exact:
             assert took == (kind if last is None else last), took
+            left, fast = ws.clone(), took
+        else:
+            assert torch.equal(ws, ws0), "the exact decoder alone wrote the workspace"
         res.append((out.cpu().numpy(), sz.cpu().numpy(), st.cpu().numpy(), ws[: 4 * (count + 1)].cpu().numpy().view(np.uint32)))
     (out, sz, st, w), (xout, xsz, xst, _) = res
     bad = set()
@@ -223,3 +233,6 @@ def _run(cuda, ins, jc=None, slots=None, handed="auto", hints=None, lead=5, kind
         assert int(w[0]) == len(got)
         expect = bad if handed == "auto" else (set(range(count)) if handed == "all" else set(handed))
         assert got == expect, (sorted(got), sorted(expect))
+    assert np.array_equal(whole.cpu().numpy()[GUARD + pad : GUARD + pad + total_in], np.frombuffer(b"".join(ins), np.uint8)), "the input was written"
+    nh, _, nd, _ = k2_lists(left, count)
+    return left, nh, (nd if fast in ("t", "w") else 0)  # (K2r and K2j defer nothing: the word is not theirs)

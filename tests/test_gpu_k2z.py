@@ -27,14 +27,19 @@ def _ample(b):
     return max(1 << 20, 4 * len(b))
 
 
-def _run_size(cuda, ins, design=(), limit=0, hints=HINTS, expect=None, handed="auto", route=None):
+def _run_size(cuda, ins, design=(), limit=0, hints=HINTS, expect=None, handed="auto", route=None, ws_init=0, keep=None):
     """expect: {index: (size, status)} instead of the oracle's answer (a stream too large for it);
     design: indices of valid streams the fast parse hands over by design; handed=None: the slow list
     is not checked; route: {hint: what ez_decompressed_size_chunk_last must report} where that is not
-    the hint's chunk (1: the lane-per-stream kernel).  Returns the (sizes, statuses) of the first run."""
+    the hint's chunk (1: the lane-per-stream kernel).  ws_init: what the workspace holds when a call
+    starts (a fill byte, or a tensor to copy from); it lies between two guards (tests/dirty.py) that
+    must be intact afterwards, and the exact decoder alone must leave it as it was.  keep: a list
+    that receives the workspace of every run of the fast kernel as it left it.
+    Returns the (sizes, statuses) of the first run."""
     import torch
 
     import eazy_amd as ez
+    from dirty import guarded, guards_intact
 
     count = len(ins)
     coff = LEAD + np.concatenate([[0], np.cumsum([len(b) for b in ins])]).astype(np.int64)
@@ -57,9 +62,11 @@ def _run_size(cuda, ins, design=(), limit=0, hints=HINTS, expect=None, handed="a
         for exact in (False, True):
             sz = torch.full((count + 1,), -7, dtype=torch.int64, device=cuda)
             st = torch.full((count + 1,), -7, dtype=torch.int32, device=cuda)
-            ws = torch.zeros(ez._lib().ez_decompress_workspace(count), dtype=torch.uint8, device=cuda)
+            ws_whole, ws = guarded(cuda, ez._lib().ez_decompress_workspace(count), ws_init)
+            ws0 = ws.clone()
             ez.decompressed_sizes(comp, d_coff, block_size_limit=limit, sizes=sz, status=st, workspace=ws, exact_only=exact, max_len=hint)
             torch.cuda.synchronize()
+            guards_intact(ws_whole, f"hint {hint}, exact {exact}")
             ran = route[hint] if route and hint in route else ez.decompressed_size_chunk(hint)
             assert ez.decompressed_size_chunk_last() == (0 if exact else ran), (hint, exact)
             sz, st = sz.cpu().numpy(), st.cpu().numpy()
@@ -71,8 +78,10 @@ def _run_size(cuda, ins, design=(), limit=0, hints=HINTS, expect=None, handed="a
                 got = set(int(x) for x in w[1 : 1 + int(w[0])])
                 assert int(w[0]) == len(got)
                 assert got == bad, (hint, sorted(got), sorted(bad))
+            if keep is not None and not exact:
+                keep.append(ws.clone())
             if exact:
-                assert int(w[0]) == 0  # (the workspace is not used)
+                assert torch.equal(ws, ws0)  # (the workspace is not used: with the default, its first word stays 0)
             if first is None:
                 first = (sz[:count].copy(), st[:count].copy())
             assert np.array_equal(first[0], sz[:count]) and np.array_equal(first[1], st[:count]), (hint, exact)

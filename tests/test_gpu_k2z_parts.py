@@ -29,15 +29,19 @@ def _parts(ins, C):
     return sum((len(b) + 64 * C - 1) // (64 * C) for b in ins)
 
 
-def _query(cuda, comp, d_coff, count, hint, route, in_bytes, limit=0):
-    """One query -> (sizes, statuses, slow set, parts_last, chunk_last), the arrays' edges checked."""
+def _query(cuda, comp, d_coff, count, hint, route, in_bytes, limit=0, ws_init=0, keep=None):
+    """One query -> (sizes, statuses, slow set, parts_last, chunk_last), the arrays' edges checked.
+    ws_init: what the workspace holds when the call starts (a fill byte, or a tensor to copy from);
+    it lies between two guards (tests/dirty.py), intact afterwards.  keep: a list that receives the
+    workspace as the query left it."""
     import torch
 
     import eazy_amd as ez
+    from dirty import guarded, guards_intact
 
     sz = torch.full((count + 2 * EDGE,), -7, dtype=torch.int64, device=cuda)
     st = torch.full((count + 2 * EDGE,), -7, dtype=torch.int32, device=cuda)
-    ws = torch.zeros(ez._lib().ez_decompress_workspace(count), dtype=torch.uint8, device=cuda)
+    ws_whole, ws = guarded(cuda, ez._lib().ez_decompress_workspace(count), ws_init)
     ez.select_size_route(route)
     try:
         ez.decompressed_sizes(comp, d_coff, block_size_limit=limit, sizes=sz[EDGE : EDGE + count], status=st[EDGE : EDGE + count],
@@ -47,6 +51,9 @@ def _query(cuda, comp, d_coff, count, hint, route, in_bytes, limit=0):
         chunk = ez.decompressed_size_chunk_last()
     finally:
         ez.select_size_route("")
+    guards_intact(ws_whole, f"route {route!r}, hint {hint}")
+    if keep is not None:
+        keep.append(ws.clone())
     sz, st = sz.cpu().numpy(), st.cpu().numpy()
     for a in (sz, st):
         assert (a[:EDGE] == -7).all() and (a[EDGE + count :] == -7).all(), route
@@ -81,8 +88,9 @@ def _want(ins, expect=None, limit=0):
     return want
 
 
-def _run_parts(cuda, ins, design=(), chunks=(256, 1024), expect=None, limit=0):
-    """-> {C: (parts walked, taken as recorded, walked again)} of the parts route's runs."""
+def _run_parts(cuda, ins, design=(), chunks=(256, 1024), expect=None, limit=0, ws_init=0, keep=None):
+    """-> {C: (parts walked, taken as recorded, walked again)} of the parts route's runs.
+    ws_init, keep: _query's."""
     count = len(ins)
     whole, comp, d_coff, nin = _upload(cuda, ins)
     want = _want(ins, expect, limit)
@@ -90,7 +98,7 @@ def _run_parts(cuda, ins, design=(), chunks=(256, 1024), expect=None, limit=0):
     got = {}
     for C in chunks:
         for route in ("v", "p"):
-            sz, st, slow, last, chunk = _query(cuda, comp, d_coff, count, HINT[C], route, nin, limit)
+            sz, st, slow, last, chunk = _query(cuda, comp, d_coff, count, HINT[C], route, nin, limit, ws_init, keep)
             assert chunk == C, (C, route, chunk)
             for s in range(count):
                 assert (int(sz[s]), int(st[s])) == want[s], (C, route, s, int(sz[s]), int(st[s]), want[s])
@@ -101,6 +109,7 @@ def _run_parts(cuda, ins, design=(), chunks=(256, 1024), expect=None, limit=0):
                 assert last[0] == _parts(ins, C), (C, last, _parts(ins, C))
                 assert last[1] + last[2] <= last[0]
                 got[C] = last
+    assert np.array_equal(whole.cpu().numpy()[GUARD + LEAD : GUARD + LEAD + nin], np.frombuffer(b"".join(ins), np.uint8)), "the input was written"
     return got
 
 

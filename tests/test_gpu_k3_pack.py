@@ -345,9 +345,11 @@ def first_bad_stream(b, got, want, poff):
     return f"first wrong byte at packed[{i}] (got {got[i]:#04x}, expected {want[i]:#04x}), stream {s} of {b.sizes[s]} bytes at +{i - poff[s]}"
 
 
-def run_pack(cuda, b, src_shift=0, dst_shift=0, covers=None):
+def run_pack(cuda, b, src_shift=0, dst_shift=0, covers=None, ws_init=None):
     """ez.pack on the batch with the slots view at src_shift and the packed view at dst_shift
-    mod 4 -> asserts the reference's offsets and bytes and that nothing else was written."""
+    mod 4 -> asserts the reference's offsets and bytes and that nothing else was written.
+    ws_init: a tensor whose first bytes the workspace holds when the call starts (an earlier pack's
+    workspace; None: FILL).  Returns the workspace as the call left it."""
     import torch
 
     import eazy_amd as ez
@@ -374,6 +376,9 @@ def run_pack(cuda, b, src_shift=0, dst_shift=0, covers=None):
 
     nws = ez._lib().ez_pack_workspace(count)
     wbuf = torch.full((GUARD + nws + GUARD,), FILL, dtype=torch.uint8, device=cuda)
+    if ws_init is not None:
+        n = min(nws, ws_init.numel())
+        wbuf[GUARD : GUARD + n].copy_(ws_init[:n])
     obuf = torch.full((8 + count + 1 + 8,), OFF_FILL, dtype=torch.int64, device=cuda)
     slot_off = torch.from_numpy(b.slot_off).to(cuda)
     sizes = torch.from_numpy(b.sizes).to(cuda)
@@ -399,6 +404,7 @@ def run_pack(cuda, b, src_shift=0, dst_shift=0, covers=None):
     assert sbuf.cpu().numpy().tobytes() == sbuf_h.tobytes(), f"{what}: slots changed"
     assert np.array_equal(slot_off.cpu().numpy(), b.slot_off), f"{what}: slot_off changed"
     assert np.array_equal(sizes.cpu().numpy(), b.sizes), f"{what}: sizes changed"
+    return wbuf[GUARD : GUARD + nws].clone()
 
 
 # ------------------------------------------------------------------ P1

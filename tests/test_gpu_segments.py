@@ -72,14 +72,17 @@ def _inputs(cuda, ins, caps):
     return comp[: len(comp) - 16], torch.from_numpy(coff).to(cuda), torch.from_numpy(ooff).to(cuda), coff, ooff
 
 
-def _query(cuda, comp, d_coff, d_ooff, count, cap, limit=0, max_len=0):
+def _query(cuda, comp, d_coff, d_ooff, count, cap, limit=0, max_len=0, ws_init=0xA5, keep=None):
     """ez_stream_segments_batch into guarded arrays -> (seg_idx, seg_in, seg_out, seg_total) as numpy,
-    seg_in / seg_out whole (cap + 1 entries); the guards and the entries past the written ones are checked."""
+    seg_in / seg_out whole (cap + 1 entries); the guards and the entries past the written ones are checked.
+    ws_init: what the workspace holds when the call starts (a fill byte, or a tensor to copy from), between
+    its two guards (tests/dirty.py); keep: a list that receives the workspace as the query left it."""
     import torch
+    from dirty import guarded, guards_intact
 
     L = ez._lib()
     arrs = [_guarded(cuda, n, torch.int64) for n in (count + 1, cap + 1, cap + 1, 2)]
-    ws_whole, ws = _guarded(cuda, L.ez_segments_workspace(count), torch.uint8)
+    ws_whole, ws = guarded(cuda, L.ez_segments_workspace(count), ws_init)
     b = ez._Batch(comp.data_ptr(), d_coff.data_ptr(), None, d_ooff.data_ptr(), None, None, count, max_len, 0, 0)
     st = L.ez_stream_segments_batch(limit, C.byref(b), arrs[0][1].data_ptr(), arrs[1][1].data_ptr(), arrs[2][1].data_ptr(), cap,
                                     arrs[3][1].data_ptr(), ws.data_ptr(), ez._stream_ptr(None))
@@ -91,8 +94,9 @@ def _query(cuda, comp, d_coff, d_ooff, count, cap, limit=0, max_len=0):
         w = whole.cpu().numpy()
         assert (w[:8] == a5).all() and (w[-8:] == a5).all()
         out.append(view.cpu().numpy())
-    w = ws_whole.cpu().numpy()
-    assert (w[:8] == 0xA5).all() and (w[-8:] == 0xA5).all()
+    guards_intact(ws_whole, "the segment query")
+    if keep is not None:
+        keep.append(ws.clone())
     written = int(out[3][0])
     assert (out[1][written + 1 :] == a5).all() and (out[2][written + 1 :] == a5).all()
     return out
@@ -172,14 +176,18 @@ def test_query_edges(cuda, dumped):
     assert int(arr.sum()) == 0
 
 
-def _decode_both(cuda, ins, caps, limit=0):
+def _decode_both(cuda, ins, caps, limit=0, scratch=None):
     """The segmented decode and the exact decoder on one batch: equal sizes, statuses and bytes,
     sentinels intact outside every slot and in the slack of the streams that end OK, the OK streams'
-    bytes the oracle's.  Returns (sizes, statuses, the first decoder of the segmented decode)."""
+    bytes the oracle's.  scratch: the segmented decode's workspace is the library's own, so the
+    counterpart of the other runners' ws_init is a fill byte for ez.fill_cached, applied right before
+    the segmented decode (None: the scratch as the calls before left it).
+    Returns (sizes, statuses, the first decoder of the segmented decode)."""
     import torch
 
     count = len(ins)
     comp, d_coff, d_ooff, coff, ooff = _inputs(cuda, ins, caps)
+    host_in = comp.cpu().numpy().copy()
     res = []
     for exact in (False, True):
         out = torch.full((int(ooff[-1]) + 64,), 0xA5, dtype=torch.uint8, device=cuda)
@@ -188,6 +196,8 @@ def _decode_both(cuda, ins, caps, limit=0):
         if exact:
             ez.decompress_batch(comp, d_coff, d_ooff, block_size_limit=limit, out=out, sizes=sz, status=st, exact_only=True)
         else:
+            if scratch is not None:
+                ez.fill_cached(scratch)
             ez.decompress_batch_segmented(comp, d_coff, d_ooff, block_size_limit=limit, out=out, sizes=sz, status=st)
             took = ez.decompress_kernel_last()
         torch.cuda.synchronize()
@@ -211,6 +221,7 @@ def _decode_both(cuda, ins, caps, limit=0):
     for name, a in (("segmented", out), ("exact", xout)):
         stray = np.flatnonzero(~inside & (a != 0xA5))
         assert stray.size == 0, (name, stray[:8])
+    assert np.array_equal(comp.cpu().numpy(), host_in), "the input was written"
     return sz, st, took
 
 

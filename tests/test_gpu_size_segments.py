@@ -4,8 +4,9 @@ then decodes them segment by segment.
 
 The streams are the host check's (tools/k2_segs_check.hip --dump), grouped by BlockSizeLimit, plus one
 of them with several cuts truncated at each of its last 27 bytes, an empty stream and a header-only
-one.  Every query runs on a sub-batch view (in_off[0] != 0) with sizes, statuses and the workspace
-between 0xA5 guards (the workspace itself starts as 0xA5 too), and must report exactly what
+one.  Every query runs on a sub-batch view (in_off[0] != 0) with sizes and statuses between 0xA5
+guards and the workspace between the guards of tests/dirty.py (the workspace itself starts as 0xA5
+unless the caller says otherwise), and must report exactly what
 decompressed_sizes(exact_only=True) reports; the stage's counters must add up, equal the first slow
 list's length, and show at least the streams with a cut, no stop and status OK as sized by the stage.
 The wave route at every chunk size, the lane route and the forced parts route are covered, then
@@ -54,9 +55,12 @@ def _truncations(dumped):
     return [b[: len(b) - k] for k in range(1, 28)]
 
 
-def _query(cuda, ins, limit=0, hint=0, in_bytes=False, route="", want_chunk=None):
-    """One guarded query and the exact decoder's answer -> (sizes, statuses, (taken, sized, handed on))."""
+def _query(cuda, ins, limit=0, hint=0, in_bytes=False, route="", want_chunk=None, ws_init=0xA5, keep=None):
+    """One guarded query and the exact decoder's answer -> (sizes, statuses, (taken, sized, handed on)).
+    ws_init: what the workspace holds when the call starts (a fill byte, or a tensor to copy from),
+    between its two guards (tests/dirty.py); keep: a list that receives the workspace as the query left it."""
     import torch
+    from dirty import guarded, guards_intact
 
     count = len(ins)
     coff = PAD + np.concatenate([[0], np.cumsum([len(b) for b in ins])]).astype(np.int64)
@@ -65,7 +69,7 @@ def _query(cuda, ins, limit=0, hint=0, in_bytes=False, route="", want_chunk=None
     d_coff = torch.from_numpy(coff).to(cuda)
     sz_whole, sz = _guarded(cuda, max(count, 1), torch.int64)  # (count == 0: one element, so that the pointers are not NULL)
     st_whole, st = _guarded(cuda, max(count, 1), torch.int32)
-    ws_whole, ws = _guarded(cuda, ez._lib().ez_decompress_workspace(count), torch.uint8)
+    ws_whole, ws = guarded(cuda, ez._lib().ez_decompress_workspace(count), ws_init)
     ez.select_size_route(route)
     try:
         ez.decompressed_sizes(comp, d_coff, block_size_limit=limit, sizes=sz, status=st, workspace=ws, max_len=hint,
@@ -78,7 +82,10 @@ def _query(cuda, ins, limit=0, hint=0, in_bytes=False, route="", want_chunk=None
         assert chunk == want_chunk
     if route == "p" and count:
         assert chunk in (256, 1024) and parts[0] > 0, (chunk, parts)
-    for whole, n in ((sz_whole, count), (st_whole, count), (ws_whole, ws.numel())):
+    guards_intact(ws_whole, f"hint {hint}, route {route!r}")
+    if keep is not None:
+        keep.append(ws.clone())
+    for whole, n in ((sz_whole, count), (st_whole, count)):
         raw = whole.view(torch.uint8).cpu().numpy()
         edge = 8 * whole.element_size()
         assert (raw[:edge] == 0xA5).all() and (raw[edge + n * whole.element_size() :] == 0xA5).all()
