@@ -32,12 +32,8 @@ constexpr int32_t kWChunk = 1024;  // output leaves the ring this many bytes at 
 constexpr size_t kWLds = 16 + (size_t)kWR + 32 + kWIn + 16 + 12 * kDefSlots;  // rings, deferred literals
 // Long literals (C4: a whole fp32 bucket is one literal) are not moved through the ring by the
 // stream's one wave (1 KiB per pass, one HBM round trip each): their tag is parsed, the ring gets
-// their last 8 KiB, and kd_copy moves their bytes with the whole chip afterwards.  A far copy
+// their last 8 KiB, and kd_copy (ez_decompress_tok.hip) moves their bytes with the whole chip afterwards.  A far copy
 // reading from such a literal before kd_copy has run reads its bytes from the input instead.
-
-__device__ __forceinline__ V16 ld_in(const uint8_t *y, const uint8_t *lo, const uint8_t *hi) {
-    return y + 16 <= hi ? ld16v(y) : ld_clamped(y, lo, hi);
-}
 
 // stream s by the whole wave; false = hand it over
 __device__ bool wave_one(const DecompressArgs &A, const uint64_t s, uint8_t *ring, uint8_t *inb, int32_t *defs, const int lane) {
@@ -211,26 +207,14 @@ __device__ bool wave_one(const DecompressArgs &A, const uint64_t s, uint8_t *rin
                 // a long literal: the bytes before it leave the ring exactly, the ring gets its last
                 // kWR bytes, kd_copy moves it (the record's slot from the batch-wide counter)
                 run_group();
-                for (int32_t q = fl + 16 * lane; q < pos; q += 1024) {
-                    const V16 v = rld<kWR>(ring, q);
-                    if (q + 16 <= pos) st16v(out + q, v);
-                    else put_small(out + q, v, (uint32_t)(pos - q));
-                }
+                flush_exact<kWR>(ring, out, fl, pos, lane);
                 const int32_t tail = L - kWR;  // >= 0: kDeferMin > kWR
 #pragma unroll
                 for (int32_t k = 0; k < kWR / 1024; k++) {
                     const int32_t q = tail + 1024 * k + 16 * lane;
                     rst<kWR>(ring, pos + q, ld_in(b + src + q, A.in, in_end));
                 }
-                if (lane == 0) {
-                    const uint32_t at = atomicAdd(&A.defer[0], 1u);
-                    if (at < A.defer_cap) ((DeferLit *)(A.defer + 4))[at] = DeferLit{A.in_off[s] + (uint64_t)src, A.out_off[s] + (uint64_t)pos, (uint64_t)L};
-                }
-                if (lane == 0) {
-                    defs[3 * nd] = pos;
-                    defs[3 * nd + 1] = src;
-                    defs[3 * nd + 2] = L;
-                }
+                defer_record(A, s, defs, nd, pos, src, L, lane);
                 nd++;
                 pos += L;
                 fl = pos;
@@ -278,11 +262,7 @@ __device__ bool wave_one(const DecompressArgs &A, const uint64_t s, uint8_t *rin
         run_group();  // before the input ring moves on
         i += p;
     }
-    for (int32_t q = fl + 16 * lane; q < pos; q += 1024) {  // the last partial chunk, exact bytes
-        const V16 v = rld<kWR>(ring, q);
-        if (q + 16 <= pos) st16v(out + q, v);
-        else put_small(out + q, v, (uint32_t)(pos - q));
-    }
+    flush_exact<kWR>(ring, out, fl, pos, lane);  // the last partial chunk
     if (lane == 0) {
         A.out_size[s] = (uint64_t)pos;
         if (A.status) A.status[s] = EZ_OK;
@@ -301,34 +281,7 @@ __global__ __launch_bounds__(64) void k2_wave(DecompressArgs A) {
         }
 }
 
-// every deferred literal's bytes, 64 KiB pieces per block step
-__global__ __launch_bounds__(256) void kd_copy(DecompressArgs A, uint64_t kp) {
-    const uint64_t nl = A.defer[0] < A.defer_cap ? A.defer[0] : A.defer_cap;
-    const DeferLit *rec = (const DeferLit *)(A.defer + 4);
-    const uint8_t *lo = A.in, *hi = A.in + A.in_off[A.count];
-    for (uint64_t q = blockIdx.x; q < nl * kp; q += gridDim.x) {
-        const DeferLit L = rec[q / kp];
-        // kp is a hint (the caller's largest slot): a longer literal's block takes every kp-th piece
-        for (uint64_t b = (q % kp) * 65536; b < L.len; b += kp * 65536) {
-            const uint64_t e = b + 65536 < L.len ? b + 65536 : L.len;
-            for (uint64_t k = b + 16 * threadIdx.x; k < e; k += 16 * 256) {
-                const uint8_t *y = A.in + L.src + k;
-                const V16 v = y + 16 <= hi ? ld16v(y) : ld_clamped(y, lo, hi);
-                if (k + 16 <= e) st16v(A.out + L.dst + k, v);
-                else put_small(A.out + L.dst + k, v, (uint32_t)(e - k));
-            }
-        }
-    }
-}
-
 }  // namespace
-
-hipError_t launch_defer_copy(const DecompressArgs &a, hipStream_t st) {
-    // pieces per record: the largest output slot bounds a literal (max_out 0: unknown, take 1 GiB)
-    const uint64_t mo = a.max_out ? a.max_out : (1ull << 30);
-    hipLaunchKernelGGL(kd_copy, dim3(2048), dim3(256), 0, st, a, (mo + 65535) / 65536);
-    return hipGetLastError();
-}
 
 hipError_t launch_decompress_wave(const DecompressArgs &a, hipStream_t st) {
     const uint64_t grid = a.count < (1u << 30) ? a.count : (1u << 30);

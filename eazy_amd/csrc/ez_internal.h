@@ -23,7 +23,7 @@ inline int knob(const char *, int dflt) { return dflt; }
 struct SpecState {
     uint32_t from, done, op, flags;
 };
-// K2w: a long literal kd_copy moves after the decoders (len bytes from in[src] to out[dst])
+// K2t, K2w: a long literal kd_copy moves after the decoders (len bytes from in[src] to out[dst])
 struct DeferLit {
     uint64_t src, dst, len;
 };
@@ -113,7 +113,7 @@ struct DecompressArgs {
     int64_t boff;             // handle: absolute offset of in[0]
     DecodeState *st;          // handle: state in/out
     uint32_t *slow;           // batch: [0] = count, [1..] = streams the fast path handed over (nullptr = exact path only)
-    uint32_t *defer;          // K2w: [0] = count, records (DeferLit) from word 4: long literals kd_copy moves
+    uint32_t *defer;          // K2t, K2w: [0] = count, records (DeferLit) from word 4: long literals kd_copy moves
     uint64_t defer_cap;       // records reserved
     uint64_t max_out;         // batch: host hint, largest output slot (0 = unknown)
     const uint32_t *todo;     // batch: [0] = count, [1..] = the streams to decode (nullptr = all)
@@ -221,7 +221,7 @@ int last_decompress_variant();  // the first K2 kernel of the last batch decode
 // K2r: one lane per stream with a 512-byte LDS ring of recent output (ez_decompress_ring.hip)
 hipError_t launch_decompress_ring(const DecompressArgs &a, hipStream_t s);
 hipError_t launch_decompress_wave(const DecompressArgs &a, hipStream_t s);  // K2w, long streams
-hipError_t launch_defer_copy(const DecompressArgs &a, hipStream_t s);       // K2w's deferred literals
+hipError_t launch_defer_copy(const DecompressArgs &a, hipStream_t s);       // kd_copy: K2t's (and K2w's) deferred literals
 // K2j (ez_decompress_jump.hip): batches of at most 1,024 streams, chip-wide token starts, token
 // records and pointer jumping over the copied bytes; streams it cannot take go to slow
 bool jump_applies(const DecompressArgs &a);
