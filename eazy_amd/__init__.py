@@ -1006,8 +1006,26 @@ def decompressed_sizes(comp, comp_off, block_size_limit: int = 0, sizes=None, st
     return sizes, status
 
 
+def select_segments_route(kind: str = "") -> None:
+    """Force the route of later stream_segments / decompress_batch_segmented queries ('p' the parts
+    route at any stream length, given in_bytes; 'v' never the parts route; '' = automatic).  Tests
+    and A/B only."""
+    _check(_lib().ez_select_segments_route(ord(kind) if kind else 0))
+
+
+def segments_parts_last() -> tuple[int, int, int, int]:
+    """Of the last stream_segments or decompressed_sizes call (whichever came later; the size query's
+    stage fills nothing), after its stream was synchronised: parts walked by the parts route's first pass, parts taken as recorded, parts walked again, parts whose cuts the fill pass
+    wrote (zeros: the route did not run, or found in_bytes too small)."""
+    c = (C.c_uint64 * 4)()
+    L = _lib()
+    L.ez_segments_parts_last.argtypes = [C.POINTER(C.c_uint64)]
+    _check(L.ez_segments_parts_last(c))
+    return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
+
 def stream_segments(comp, comp_off, out_off, block_size_limit: int = 0, seg_cap: int | None = None, max_len: int = 0,
-                    stream=None):
+                    stream=None, in_bytes: int = 0):
     """K2g: where the streams comp[comp_off[s]:comp_off[s+1]] can be cut at a MetaReset after output
     (concatenated streams, a Writer that was Reset) -> (seg_idx, seg_in, seg_out, seg_total), int64
     CUDA tensors.  Stream s owns the segments seg_idx[s] .. seg_idx[s+1]-1; segment g is
@@ -1018,6 +1036,8 @@ def stream_segments(comp, comp_off, out_off, block_size_limit: int = 0, seg_cap:
     segment per stream and seg_total = (count, found).  None: some room, and where it was too little
     the call reads seg_total back (which waits for the stream) and asks again with enough.  max_len is
     an optional host hint, the longest INPUT stream in bytes: it picks the chunk size and nothing else.
+    in_bytes is an optional host hint, comp_off[-1] - comp_off[0] or more: with it the parts route (a
+    long stream's chain cut over many waves) can run; a wrong value costs speed, never results.
     Asynchronous on the stream when seg_cap is given."""
     import torch
 
@@ -1027,7 +1047,7 @@ def stream_segments(comp, comp_off, out_off, block_size_limit: int = 0, seg_cap:
     L = _lib()
     cap = 2 * count + 64 if seg_cap is None else seg_cap  # (seg_cap < count: the library refuses it)
     ws = torch.empty(L.ez_segments_workspace(count), dtype=torch.uint8, device=dev)
-    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, out_off.data_ptr(), None, None, count, max_len, 0, 0)
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, out_off.data_ptr(), None, None, count, max_len, in_bytes, 0)
     seg_idx = torch.empty(count + 1, dtype=torch.int64, device=dev)
     seg_total = torch.empty(2, dtype=torch.int64, device=dev)
     while True:
@@ -1045,13 +1065,15 @@ def stream_segments(comp, comp_off, out_off, block_size_limit: int = 0, seg_cap:
     return seg_idx, seg_in, seg_out, seg_total
 
 
-def decompress_batch_segmented(comp, comp_off, out_off, block_size_limit: int = 0, out=None, sizes=None, status=None, stream=None):
+def decompress_batch_segmented(comp, comp_off, out_off, block_size_limit: int = 0, out=None, sizes=None, status=None, stream=None,
+                               in_bytes: int | None = None):
     """decompress_batch for batches whose streams may be concatenated (a MetaReset after output: a
     Writer that was Reset, streams joined back to back) -> (out, sizes, status), the same results with
     every segment on the fast decoders: stream_segments into the library's own scratch, one read-back
     (which waits for the stream), the batch decoders over the segments, and the per-stream merge of
     their sizes and statuses.  A batch without such a Reset costs the query and then decompress_batch's
-    decode."""
+    decode.  in_bytes is a host hint for the query's parts route, comp_off[-1] - comp_off[0] or more
+    (None: comp's length, which is never less; 0: unknown); a wrong value costs speed, never results."""
     import torch
 
     _need_cuda(comp, comp_off, out_off)
@@ -1063,7 +1085,9 @@ def decompress_batch_segmented(comp, comp_off, out_off, block_size_limit: int = 
         sizes = torch.empty(count, dtype=torch.int64, device=dev)
     if status is None:
         status = torch.empty(count, dtype=torch.int32, device=dev)
-    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), out.data_ptr(), out_off.data_ptr(), sizes.data_ptr(), status.data_ptr(), count, 0, 0, 0)
+    if in_bytes is None:
+        in_bytes = comp.numel()
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), out.data_ptr(), out_off.data_ptr(), sizes.data_ptr(), status.data_ptr(), count, 0, in_bytes, 0)
     _check(_lib().ez_decompress_batch_segmented(block_size_limit, C.byref(b), None, _stream_ptr(stream)))
     return out, sizes, status
 
@@ -1105,7 +1129,7 @@ def decompress_batch_sized(comp, comp_off, block_size_limit: int = 0, stream=Non
             total, largest, in_bytes, joined = (int(v) for v in back)
         out = torch.empty(total + 16, dtype=torch.uint8, device=dev)
         if joined:
-            _, sizes, status = decompress_batch_segmented(comp, comp_off, out_off, block_size_limit, out=out, stream=stream)
+            _, sizes, status = decompress_batch_segmented(comp, comp_off, out_off, block_size_limit, out=out, stream=stream, in_bytes=in_bytes)
         else:
             _, sizes, status = decompress_batch(comp, comp_off, out_off, block_size_limit, out=out, workspace=ws, stream=stream,
                                                 max_len=largest, in_bytes=in_bytes, out_bytes=total)

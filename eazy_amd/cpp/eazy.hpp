@@ -766,7 +766,9 @@ inline Err DecompressedSizeBatch(int64_t block_size_limit, const ez_batch &b, vo
 // seg_idx[s+1]-1; segment g is in[seg_in[g] .. seg_in[g+1]) decoded into out[seg_out[g] .. seg_out[g+1]);
 // seg_total = {segments written, segments found} (more found than seg_cap: one segment per stream).
 // Device arrays: seg_idx[count+1], seg_in and seg_out[seg_cap+1], seg_total[2], workspace of
-// ez_segments_workspace(count) bytes; b.max_len is the longest INPUT stream (0: unknown).
+// ez_segments_workspace(count) bytes; b.max_len is the longest INPUT stream (0: unknown); b.in_bytes is
+// in_off[count] - in_off[0] or more (0: unknown), with which the parts route (a long stream's chain cut
+// over many waves) can run: a wrong value costs speed, never results.
 inline Err StreamSegments(int64_t block_size_limit, const ez_batch &b, uint64_t *seg_idx, uint64_t *seg_in, uint64_t *seg_out,
                           uint64_t seg_cap, uint64_t *seg_total, void *workspace, void *hip_stream) {
     const int st = ez_stream_segments_batch(block_size_limit, &b, seg_idx, seg_in, seg_out, seg_cap, seg_total, workspace, hip_stream);
@@ -775,10 +777,26 @@ inline Err StreamSegments(int64_t block_size_limit, const ez_batch &b, uint64_t 
 }
 // ez_decompress_batch_segmented: DecompressBatch for batches whose streams may be concatenated, with
 // every segment on the fast decoders; the same out, out_size and status.  It keeps its own scratch
-// and waits for the stream once (the read-back of the segment count).
+// and waits for the stream once (the read-back of the segment count).  b.in_bytes is the query's hint
+// as for StreamSegments: the compressed buffer's length will do.
 inline Err DecompressBatchSegmented(int64_t block_size_limit, const ez_batch &b, void *hip_stream) {
     const int st = ez_decompress_batch_segmented(block_size_limit, &b, nullptr, hip_stream);
     if (st == EZ_EINVAL) throw std::invalid_argument("eazy: DecompressBatchSegmented: in_off, out_off and out_size are required");
+    return (Err)st;
+}
+// ez_select_segments_route: the route of later segment queries ('p' the parts route at any stream
+// length, given b.in_bytes; 'v' never the parts route; 0 automatic).  Tests and A/B only.
+inline Err SelectSegmentsRoute(int kind) {
+    const int st = ez_select_segments_route(kind);
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: SelectSegmentsRoute: kind is 'p', 'v' or 0");
+    return (Err)st;
+}
+// ez_segments_parts_last: of the last StreamSegments or DecompressedSizeBatch call (whichever came later;
+// the size query's stage fills nothing), whose stream the caller has synchronised, {parts walked in the
+// first pass, records taken as they stood, parts walked again, parts filled}
+inline Err SegmentsPartsLast(uint64_t counts[4]) {
+    const int st = ez_segments_parts_last(counts);
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: SegmentsPartsLast: counts is required");
     return (Err)st;
 }
 // ez_segments_last: of the last DecompressBatchSegmented call, {segments decoded, handed to the exact

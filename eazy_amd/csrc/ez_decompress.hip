@@ -355,7 +355,7 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
     g_last_size_chunk = chunk;
     if ((e = launch_size_fast(a, chunk, st)) != hipSuccess) return e;
     // K2g's walk sizes the concatenated streams of the list; the exact decoder gets the second list
-    if ((e = launch_size_segs(a, max_len, st)) != hipSuccess) return e;
+    if ((e = launch_size_segs(a, max_len, st, a0.jws == nullptr)) != hipSuccess) return e;
     a.slow = second;
     const uint64_t exact_grid = a.count < 4096 ? a.count : 4096;
     hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);

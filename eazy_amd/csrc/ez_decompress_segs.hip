@@ -24,6 +24,9 @@
 //   heads    a thread per stream: each stream's first segment, the kept cuts, the arrays' ends;
 //   fill     the walk again, only for streams with more than kGKeep cuts, which writes them in place.
 // A stream without a Reset after output is walked once.
+// With the caller's in_bytes hint, few long streams take the parts route instead
+// (ez_decompress_segs_parts.hip: its passes go before the count pass and behind the fill pass, and the
+// walk here then skips the streams that have parts).
 // The size query (ez_decompressed_size_batch) runs the same walk in one more kernel, k2g_size, over the
 // streams its fast kernels handed over: the walk's total is a concatenated stream's decoded length.
 #include <hip/hip_runtime.h>
@@ -96,7 +99,9 @@ __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
     const int lane = lane_id();
     const int64_t limit = A.block_size_limit;
     const int32_t lim32 = k2_lim32(limit);
+    const bool parted = A.parts_gate && *A.parts_gate;  // (the parts route walks the streams that have parts)
     for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
+        if (parted && A.parts_base[s] != A.parts_base[s + 1]) continue;
         uint64_t g0 = 0, nseg = 0;
         if (FILL) {
             g0 = A.seg_idx[s];
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(64) void k2g_walk(SegsArgs A) {
 // list is only read.  ctr: {entries taken, streams sized, the second list: [0] = its length, which is
 // the streams handed on}, zeroed by the launcher.
 template <int C>
-__global__ __launch_bounds__(64) void k2g_size(DecompressArgs A, const uint32_t *first, uint32_t *ctr) {
+__global__ __launch_bounds__(64) void k2g_size(DecompressArgs A, const uint32_t *first, uint32_t *ctr, const uint32_t *gate, const uint32_t *base) {
     constexpr int W = C / 32;
     __shared__ __attribute__((aligned(16))) uint8_t stage[kz_stage_bytes(C)];
     __shared__ uint32_t bm[kZLanes][W + 1];  // (+1: the lanes' rows on distinct banks)
@@ -140,9 +145,11 @@ __global__ __launch_bounds__(64) void k2g_size(DecompressArgs A, const uint32_t 
     const int lane = lane_id();
     const int64_t limit = A.block_size_limit;
     const int32_t lim32 = k2_lim32(limit);
+    const bool parted = gate && *gate;  // (the parts route's stage sized the listed streams that have parts)
     uint32_t sized = 0;
     for (uint64_t k = blockIdx.x; k < n; k += gridDim.x) {
         const uint64_t s = first[1 + k];
+        if (parted && base[s] != base[s + 1]) continue;
         const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
         bool ok = nb64 < (1ull << 31);
         uint64_t total = 0;
@@ -205,11 +212,13 @@ __global__ __launch_bounds__(kScanThreads) void k2g_scan(SegsArgs A) {
 
 __global__ void k2g_heads(SegsArgs A) {
     const bool over = A.hdr[0] != 0;
+    const bool parted = A.parts_gate && *A.parts_gate;
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= A.count; s += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t g = A.seg_idx[s];
         A.seg_in[g] = A.in_off[s];  // (s == count: the arrays' ends)
         A.seg_out[g] = A.out_off[s];
         if (s == A.count || over) continue;
+        if (parted && A.parts_base[s] != A.parts_base[s + 1]) continue;  // (the parts route's fill writes its cuts)
         const uint64_t n = A.seg_idx[s + 1] - g;
         if (n > kGKeep + 1) continue;  // (the fill pass walks it again)
         const uint64_t o0 = A.out_off[s], o1 = A.out_off[s + 1];
@@ -269,6 +278,23 @@ hipError_t launch_segments(const SegsArgs &a0, uint64_t max_len, void *workspace
     // every wave of the chip busy at most (32 per CU); the streams beyond go round the grid
     const unsigned grid = (unsigned)(a.count < 8192 ? a.count : 8192);
     hipError_t e;
+    // The parts route (ez_decompress_segs_parts.hip) needs the batch's extent to size its records
+    // without a read-back: only with the caller's in_bytes hint, and where segs_parts_chunk picks it or
+    // it is forced.  Without its scratch the batch takes the wave route.
+    a.parts_gate = a.parts_base = nullptr;
+    const int sel = selected_segments_route();
+    int pchunk = a.count != 0 && a.in_bytes != 0 && a.count <= (1u << 20) && sel != 'v' ? segs_parts_chunk(max_len, a.count, a.in_bytes, sel == 'p') : 0;
+    CacheLease please;  // (its scratch, until the last launch)
+    if (pchunk) {
+        e = launch_segs_parts(a, pchunk, st, please);
+        if (e == hipErrorOutOfMemory) {
+            pchunk = 0;
+            a.parts_gate = a.parts_base = nullptr;
+        } else if (e != hipSuccess) {
+            return e;
+        }
+    }
+    if (!pchunk) segs_parts_none();
     if (a.count != 0) {
         if (chunk == 64) hipLaunchKernelGGL((k2g_walk<64, false>), dim3(grid), dim3(64), 0, st, a);
         else if (chunk == 1024) hipLaunchKernelGGL((k2g_walk<1024, false>), dim3(grid), dim3(64), 0, st, a);
@@ -285,6 +311,7 @@ hipError_t launch_segments(const SegsArgs &a0, uint64_t max_len, void *workspace
         else hipLaunchKernelGGL((k2g_walk<256, true>), dim3(grid), dim3(64), 0, st, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
+    if (pchunk && (e = launch_segs_parts_fill(a, pchunk, st)) != hipSuccess) return e;
     return hipSuccess;
 }
 
@@ -292,14 +319,27 @@ hipError_t launch_segments(const SegsArgs &a0, uint64_t max_len, void *workspace
 // list: 1 + count] ... [word 2 * count + 31: largest_slot's].
 uint32_t *size_segs_counters(uint32_t *slow, uint64_t count) { return slow + count + 1; }
 
-hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream_t st) {
+hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream_t st, bool parts) {
     uint32_t *ctr = size_segs_counters(a.slow, a.count);
     const int chunk = size_chunk(max_len);
+    // The parts route's stage for the listed streams that have parts, where the caller gave in_bytes
+    // (the same hint and gate as ez_stream_segments_batch's; not for a caller with its own scratch, a
+    // Reader handle).  Without its scratch k2g_size walks the whole list.
+    const uint32_t *gate = nullptr, *base = nullptr;
+    CacheLease please;
+    const int sel = selected_segments_route();
+    const int pchunk = parts && a.in_bytes != 0 && a.count <= (1u << 20) && sel != 'v' ? segs_parts_chunk(max_len, a.count, a.in_bytes, sel == 'p') : 0;
+    if (pchunk) {
+        const hipError_t e = launch_size_segs_parts(a, pchunk, st, please, &gate, &base);
+        if (e == hipErrorOutOfMemory) gate = base = nullptr;
+        else if (e != hipSuccess) return e;
+    }
+    if (!gate) segs_parts_none();
     // (a block per listed stream; the list's length is on the device: the blocks past it leave at once)
     const unsigned grid = (unsigned)(a.count < 8192 ? a.count : 8192);
-    if (chunk == 64) hipLaunchKernelGGL(k2g_size<64>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr);
-    else if (chunk == 1024) hipLaunchKernelGGL(k2g_size<1024>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr);
-    else hipLaunchKernelGGL(k2g_size<256>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr);
+    if (chunk == 64) hipLaunchKernelGGL(k2g_size<64>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr, gate, base);
+    else if (chunk == 1024) hipLaunchKernelGGL(k2g_size<1024>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr, gate, base);
+    else hipLaunchKernelGGL(k2g_size<256>, dim3(grid), dim3(64), 0, st, a, a.slow, ctr, gate, base);
     return hipGetLastError();
 }
 
@@ -330,13 +370,13 @@ struct {
 // the scratch of a segmented decode of count streams in at most cap segments
 struct SegScratch {
     uint64_t *hints, *seg_idx, *seg_in, *seg_out, *seg_size;
-    void *qws;
+    void *qws, *pws;
     uint32_t *dws;
     int32_t *seg_status;
     size_t bytes;
 };
 constexpr size_t kHintBytes = 64;  // {written, found, largest slot, in bytes, out bytes, handed over}
-SegScratch seg_scratch(uint8_t *p, uint64_t count, uint64_t cap) {
+SegScratch seg_scratch(uint8_t *p, uint64_t count, uint64_t cap, uint64_t pbytes) {
     SegScratch x;
     size_t o = 0;
     auto take = [&](size_t n) {
@@ -350,6 +390,7 @@ SegScratch seg_scratch(uint8_t *p, uint64_t count, uint64_t cap) {
     x.seg_out = (uint64_t *)take((cap + 1) * 8);
     x.seg_size = (uint64_t *)take(cap * 8);
     x.qws = take(segments_workspace_bytes(count));
+    x.pws = take(pbytes);  // (the query's parts route, carved out of this lease)
     x.dws = (uint32_t *)take(decompress_workspace_words(cap) * 4);
     x.seg_status = (int32_t *)take(cap * 4);
     x.bytes = o;
@@ -366,14 +407,19 @@ hipError_t launch_decompress_segmented(const DecompressArgs &a, hipStream_t st) 
         CacheLease lease = segs_cache().acquire(dev, (void *)st);
         // room for a segment per stream and some more, or for what the scratch held last time
         uint64_t cap = a.count + a.count / 2 + 1024;
+        // the query's parts route, where the caller's in_bytes hint lets it run
+        const uint64_t pbytes = a.in_bytes != 0 && a.count <= (1u << 20) && selected_segments_route() != 'v' &&
+                                        segs_parts_chunk(0, a.count, a.in_bytes, selected_segments_route() == 'p')
+                                    ? segs_parts_workspace_bytes(a.count, a.in_bytes)
+                                    : 0;
         for (uint64_t step = 1ull << 36; step; step >>= 1)
-            if (seg_scratch(nullptr, a.count, cap + step).bytes <= lease->cap) cap += step;
+            if (seg_scratch(nullptr, a.count, cap + step, pbytes).bytes <= lease->cap) cap += step;
         uint64_t h[5] = {0, 0, 0, 0, 0};
         SegScratch x;
         for (;;) {
-            x = seg_scratch(nullptr, a.count, cap);
+            x = seg_scratch(nullptr, a.count, cap, pbytes);
             if (!lease->ensure(x.bytes)) return hipErrorOutOfMemory;
-            x = seg_scratch((uint8_t *)lease->p, a.count, cap);
+            x = seg_scratch((uint8_t *)lease->p, a.count, cap, pbytes);
             if ((e = hipMemsetAsync(x.hints, 0, kHintBytes, st)) != hipSuccess) return e;
             SegsArgs q{};
             q.in = a.in;
@@ -386,6 +432,9 @@ hipError_t launch_decompress_segmented(const DecompressArgs &a, hipStream_t st) 
             q.seg_out = x.seg_out;
             q.seg_cap = cap;
             q.seg_total = x.hints;
+            q.in_bytes = pbytes ? a.in_bytes : 0;
+            q.pws = pbytes ? x.pws : nullptr;
+            q.pws_cap = pbytes;
             if ((e = launch_segments(q, 0, x.qws, st)) != hipSuccess) return e;
             hipLaunchKernelGGL(k2g_hints, dim3(grid_for(cap, 256, 1024)), dim3(256), 0, st, a.in_off, a.out_off, a.count, x.seg_out, x.hints);
             if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -274,10 +274,38 @@ struct SegsArgs {
     uint64_t *seg_total;      // 2
     uint32_t *hdr;            // the workspace's header and the cuts the count pass keeps (set by the launcher)
     uint64_t *keep;
+    // the parts route (ez_decompress_segs_parts.hip), optional: in_bytes, the caller's hint of in_off[count]
+    // - in_off[0] (0 = unknown: the wave route); pws / pws_cap, its scratch where the caller owns it
+    // (segs_parts_workspace_bytes), else leased per (device, HIP stream).  parts_gate, parts_base (set by
+    // the launcher): k2g_walk walks the whole batch where the device word parts_gate is 0 (the hint was
+    // too small), else only the streams s without parts (parts_base[s] == parts_base[s + 1])
+    uint64_t in_bytes;
+    void *pws;
+    uint64_t pws_cap;
+    const uint32_t *parts_gate;
+    const uint32_t *parts_base;
 };
 uint64_t segments_workspace_bytes(uint64_t count);
 // max_len: the caller's hint, the longest input stream (0 = unknown), which picks the chunk (size_chunk)
 hipError_t launch_segments(const SegsArgs &a, uint64_t max_len, void *workspace, hipStream_t s);
+// K2g's parts route: every stream's chain cut over many waves, chunk 256 or 1,024; needs a.in_bytes.
+// launch_segs_parts: init, first and order passes (seg_idx[s] for the streams with parts, the parts'
+// entry states); sets a's parts_gate / parts_base, and pws / pws_cap for launch_segs_parts_fill, which
+// goes behind k2g_scan and k2g_heads.  lease: the scratch, held until the last launch.
+// (hipErrorOutOfMemory: the scratch could not be had, nothing was launched)
+int segs_parts_chunk(uint64_t max_len, uint64_t count, uint64_t in_bytes, bool forced);  // its chunk; 0: the wave route
+hipError_t launch_segs_parts(SegsArgs &a, int chunk, hipStream_t s, CacheLease &lease);
+hipError_t launch_segs_parts_fill(const SegsArgs &a, int chunk, hipStream_t s);
+uint64_t segs_parts_workspace_bytes(uint64_t count, uint64_t in_bytes);
+// the size query's stage (launch_size_segs): the listed streams that have parts, by the first and order
+// passes; *gate, *base: for k2g_size behind it
+hipError_t launch_size_segs_parts(const DecompressArgs &a, int chunk, hipStream_t s, CacheLease &lease, const uint32_t **gate,
+                                  const uint32_t **base);
+DevCache &segs_parts_cache();
+void select_segments_route(int v);  // 0 = automatic, 'p' parts at any length, 'v' the wave route (tests, A/B)
+int selected_segments_route();
+void segs_parts_none();             // the last query did not take the parts route
+hipError_t segs_parts_last(uint64_t counts[4]);  // parts in the first pass, taken as recorded, walked again, filled
 // per stream its first segment whose status is not EZ_OK, else its last: out_size[s] = seg_out[g] -
 // out_off[s] + seg_size[g], status[s] (may be null) = seg_status[g]; slow, handed (optional): *handed =
 // slow[0], the segments the fast decoders handed over
@@ -295,7 +323,8 @@ DevCache &segs_cache();
 // the stage's words there, which the launcher zeroes first: {entries taken from the first list, streams
 // sized, the second list: its length (the streams handed on), then its entries}
 uint32_t *size_segs_counters(uint32_t *slow, uint64_t count);
-hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream_t s);
+// parts: the parts route's stage may take the listed streams that have parts (given a.in_bytes)
+hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream_t s, bool parts);
 hipError_t segments_last(uint64_t counts[3]);  // of the last segmented decode: segments, handed over, query retries
 bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once, ez_k1_probe.hip)
 bool lds_mskor_in_lane_order();     // the LDS property k1_lean's one-atomic visit relies on (checked once)

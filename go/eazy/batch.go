@@ -376,6 +376,7 @@ func DecompressBatchSegmented(streams [][]byte, caps []uint64, blockSizeLimit in
 	b := C.ez_batch{
 		in: (*C.uint8_t)(dIn), in_off: (*C.uint64_t)(dInOff), out: (*C.uint8_t)(dOut), out_off: (*C.uint64_t)(dOutOff),
 		out_size: (*C.uint64_t)(dSize), status: (*C.int32_t)(dStatus), count: C.uint64_t(count),
+		in_bytes: C.uint64_t(inOff[count]), // (the query's parts route needs the extent)
 	}
 	if st := C.ez_decompress_batch_segmented(C.int64_t(blockSizeLimit), &b, nil, nil); st != C.EZ_OK {
 		return nil, nil, toErr(st, 0)
@@ -407,6 +408,27 @@ func DecompressBatchSegmented(streams [][]byte, caps []uint64, blockSizeLimit in
 		}
 	}
 	return res, errs, nil
+}
+
+// SelectSegmentsRoute sets the route of later segment queries (ez_select_segments_route): 'p' the
+// parts route at any stream length, 'v' never the parts route, 0 automatic.  Tests and A/B only.
+func SelectSegmentsRoute(kind int) error {
+	if st := C.ez_select_segments_route(C.int(kind)); st != C.EZ_OK {
+		return toErr(st, 0)
+	}
+	return nil
+}
+
+// SegmentsPartsLast reports, of the last direct segment query or size query of this process,
+// whichever came later (ez_segments_parts_last): parts walked in the parts route's first pass,
+// records taken as they stood, parts walked again, parts filled (none by the size query's stage).
+// All zero where the route did not run.
+func SegmentsPartsLast() ([4]uint64, error) {
+	var counts [4]uint64
+	if st := C.ez_segments_parts_last((*C.uint64_t)(unsafe.Pointer(&counts[0]))); st != C.EZ_OK {
+		return counts, toErr(st, 0)
+	}
+	return counts, nil
 }
 
 // DecompressBatchSized decodes independent streams whose decoded lengths the caller does not know, on

@@ -353,19 +353,48 @@ int ez_decompressed_size_segs_last(const void *workspace, uint64_t count, uint64
  * and out_off[count].  seg_total[0] = the segments written, seg_total[1] = the segments found: where
  * those exceed seg_cap the one-segment-per-stream layout is written instead (seg_idx[s] = s, the
  * offsets equal to in_off / out_off) and seg_total = {count, found}, so that a caller can retry with room.
- * Uses b->in, in_off, out_off, count and max_len (host hint: the longest INPUT stream in bytes, 0 =
- * unknown; it picks the chunk size and nothing else).  workspace >= ez_segments_workspace(count)
- * device bytes.  EZ_EINVAL for a NULL array or workspace or seg_cap < count; count == 0 writes
+ * Uses b->in, in_off, out_off, count, max_len (host hint: the longest INPUT stream in bytes, 0 =
+ * unknown; it picks the chunk size and nothing else) and in_bytes (host hint: in_off[count] -
+ * in_off[0] or more, 0 = unknown; it enables the parts route below and nothing else: any value gives
+ * the same arrays).  workspace >= ez_segments_workspace(count) device bytes.
+ * The walk is a wave per stream, or, for the few long streams that one wave each would bound, the
+ * parts route: every stream's chain cut on K2z's fixed grid of parts of 64 chunks; a wave per part
+ * writes a record that can be applied to any incoming state (cuts, window, longest distance since the
+ * last cut, stop); a wave per stream follows the true chain through the records, walks again only the
+ * parts it enters elsewhere or in which the stream stops, and leaves every part's entry state; a wave
+ * per part that holds a Reset then writes that part's cuts in place.  The route sizes its scratch from
+ * in_bytes, so it runs only where the caller gives in_bytes (and the route is selected, see
+ * ez_select_segments_route); a kernel checks the real extent against the hint before anything indexes
+ * the scratch, and an under-stated hint leaves the whole batch to the wave route (an over-stated one
+ * only enlarges the scratch, which is kept per (device, HIP stream) and freed by ez_release_cached; if
+ * it cannot be had the call takes the wave route).  EZ_EINVAL for a NULL array or workspace or seg_cap < count; count == 0 writes
  * seg_idx[0], seg_in[0], seg_out[0] and seg_total and returns EZ_OK.
  * Asynchronous on hip_stream; never waits for the stream.  Memory touched: reads in[0 .. in_off[count])
  * as ez_decompress_batch does, in_off and out_off; no output buffer is needed; writes only
  * seg_idx[0 .. count], seg_in and seg_out[0 .. seg_total[0]], seg_total[0 .. 1] and the workspace.
  * The workspace's contents on entry are ignored: it need not be cleared, and nothing is written past
- * ez_segments_workspace(count) bytes.
- * Held by tests/test_k2_segments.py and tests/test_gpu_segments.py. */
+ * ez_segments_workspace(count) bytes; the parts route's scratch is the library's own.
+ * Held by tests/test_k2_segments.py, tests/test_gpu_segments.py, tests/test_k2_segs_parts.py and
+ * tests/test_gpu_segments_parts.py. */
 size_t ez_segments_workspace(uint64_t count);
 int ez_stream_segments_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *seg_idx, uint64_t *seg_in, uint64_t *seg_out,
                              uint64_t seg_cap, uint64_t *seg_total, void *workspace, void *hip_stream);
+/* Testing / A-B measurement: the route of later segment queries in this process (ez_stream_segments_batch
+ * and the query inside ez_decompress_batch_segmented): 'p' the parts route at any stream length (it
+ * still needs b->in_bytes; chunk 1,024 where the wave route takes 1,024, else 256), 'v' never the parts
+ * route, 0 = automatic.  EZ_EINVAL for any other value.  Not thread-safe against concurrent calls.
+ * Host function: touches no device memory. */
+int ez_select_segments_route(int kind);
+/* Introspection (tests, measurement): of the last ez_stream_segments_batch or
+ * ez_decompressed_size_batch call of this process, whichever came later (the size query's stage over
+ * the handed-over streams that have parts: it fills nothing, and a size query with a workspace that
+ * does not take the route zeroes the counters), counts[0] = parts the parts route walked in its first pass, counts[1] = parts whose record the true
+ * chain took as it stood, counts[2] = parts walked again from the true state (parts a token spans are
+ * in neither), counts[3] = parts whose cuts the fill pass wrote; all 0 where the parts route did not run
+ * or found in_bytes too small, and for the query inside ez_decompress_batch_segmented, whose scratch is
+ * that call's.  The caller has synchronised that call's stream.  Memory touched: the call reads 64
+ * bytes of the library's own scratch back from the device and writes counts[0 .. 3]; EZ_EINVAL for NULL. */
+int ez_segments_parts_last(uint64_t counts[4]);
 /* The results of a decode over segments, per stream: g = the stream's first segment whose
  * seg_status is not EZ_OK, else its last; out_size[s] = seg_out[g] - out_off[s] + seg_size[g],
  * status[s] (may be NULL) = seg_status[g].  Uses b->out_off, out_size, status and count.
@@ -380,8 +409,11 @@ int ez_segments_merge_batch(const ez_batch *b, const uint64_t *seg_idx, const ui
  * the room; ez_decompress_batch's decoders over the segments, with the library's own workspace (always
  * the fast decoders first); ez_segments_merge_batch.  A batch without any Reset after output costs the
  * query and then exactly ez_decompress_batch's decode.  Uses b->in, in_off, out, out_off, out_size
- * (required), status (may be NULL) and count; max_len, in_bytes and out_bytes are ignored (the call
- * measures them).  workspace is accepted for symmetry and may be NULL.
+ * (required), status (may be NULL), count and in_bytes (the query's hint as for
+ * ez_stream_segments_batch: in_off[count] - in_off[0] or more, 0 = unknown; an over-statement such as
+ * the compressed buffer's length only enlarges the scratch, and any value gives the same results);
+ * max_len and out_bytes are ignored (the call measures what the decode needs).  workspace is accepted
+ * for symmetry and may be NULL.
  * Memory touched: as ez_decompress_batch; nothing outside the slots, out_size and status is written. */
 int ez_decompress_batch_segmented(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
 /* Introspection (tests, measurement): of the last ez_decompress_batch_segmented call of this process,
@@ -424,8 +456,8 @@ int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in
 
 /* Frees the device scratch kept between batch calls (no reference counterpart; a caching
  * allocator's empty_cache).  The set: per (device, HIP stream), the K1 / K1c / K1x scratch of
- * ez_compress_batch and _writes, the K2j workspaces of ez_decompress_batch, the parts route's scratch
- * of ez_decompressed_size_batch, ez_decompress_batch_segmented's scratch and ez_writer_write_many's
+ * ez_compress_batch and _writes, the K2j workspaces of ez_decompress_batch, the parts routes' scratch
+ * of ez_decompressed_size_batch and ez_stream_segments_batch, ez_decompress_batch_segmented's scratch and ez_writer_write_many's
  * staging (device and pinned); per device, the Reader handles' shared K2j workspace; and the
  * multi-device calls' pooled shard buffers.  device < 0 = every device.  Scratch in use by a
  * concurrent call is kept.  Entries beyond 8 streams per device are also freed least recently used
@@ -435,7 +467,7 @@ int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in
  * and tests/test_gpu_call_order.py). */
 int ez_release_cached(int device);
 /* Testing / introspection: sets every idle buffer of the set ez_release_cached frees (the same
- * set: the per-(device, HIP stream) scratch of K1 / K1c / K1x, K2j, the parts route,
+ * set: the per-(device, HIP stream) scratch of K1 / K1c / K1x, K2j, both parts routes,
  * ez_decompress_batch_segmented and ez_writer_write_many, device and pinned; the Reader handles'
  * shared K2j workspace; the multi-device calls' pooled shard buffers) to `byte` (0..255), or touches
  * nothing and only counts with byte = -1; *bytes (may be NULL) gets the device and pinned bytes
