@@ -9,7 +9,8 @@ This module is a thin ctypes layer over it:
 * ``compress_batch`` / ``pack`` / ``decompress_batch`` drive the batched,
   device-resident kernels (K1/K3/K2) on torch CUDA tensors;
   ``stream_segments`` / ``decompress_batch_segmented`` (K2g) take batches of
-  concatenated streams.
+  concatenated streams; ``stream_breaks`` (K2b) lists every stream's Break
+  positions (``Writer.WriteBreak``'s message boundaries) without decoding.
 * ``Encoder`` / ``Decoder`` expose the token codec (writer.go:537-621,
   reader.go:346-514).
 
@@ -143,6 +144,9 @@ def _lib():
     L.ez_segments_merge_batch.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ez_decompress_batch_segmented.argtypes = [i64, vp, vp, vp]
     L.ez_segments_last.argtypes = [C.POINTER(C.c_uint64)]
+    L.ez_breaks_workspace.restype = sz
+    L.ez_breaks_workspace.argtypes = [C.c_uint64]
+    L.ez_stream_breaks_batch.argtypes = [i64, vp, vp, vp, C.c_uint64, vp, vp, vp]
     _L = L
     return L
 
@@ -1098,6 +1102,47 @@ def segments_last() -> tuple[int, int, int]:
     c = (C.c_uint64 * 3)()
     _check(_lib().ez_segments_last(c))
     return int(c[0]), int(c[1]), int(c[2])
+
+
+def stream_breaks(comp, comp_off, block_size_limit: int = 0, max_len: int = 0, brk_cap: int | None = None, workspace=None, stream=None):
+    """K2b: the Break positions of every stream comp[comp_off[s]:comp_off[s+1]] without decoding
+    (Writer.WriteBreak's markers, which the batch decoders skip) -> (brk_idx, brk_pos, sizes, status),
+    CUDA tensors.  Stream s owns brk_pos[brk_idx[s]:brk_idx[s+1]]: the bytes a Reader has produced at
+    each ErrBreak it returns before the stream's first error, in order, which are offsets into the
+    stream's decoded output (equal positions: an empty message).  sizes and status are
+    decompressed_sizes's.  brk_cap: room for that many positions; more found writes none of
+    them (brk_idx[-1], the number found, then exceeds brk_cap).  None: some room, and where it was too
+    little the call reads the totals back (which waits for the stream) and asks again with enough.
+    max_len is an optional host hint, the longest INPUT stream in bytes: it picks the chunk size and
+    nothing else.  workspace: ez_breaks_workspace(count) bytes (None: allocated here).  Asynchronous
+    on the stream when brk_cap is given."""
+    import torch
+
+    _need_cuda(comp, comp_off)
+    count = comp_off.numel() - 1
+    dev = comp.device
+    L = _lib()
+    if workspace is None:
+        workspace = torch.empty(L.ez_breaks_workspace(count), dtype=torch.uint8, device=dev)
+    sizes = torch.empty(count, dtype=torch.int64, device=dev)
+    status = torch.empty(count, dtype=torch.int32, device=dev)
+    brk_idx = torch.empty(count + 1, dtype=torch.int64, device=dev)
+    brk_total = torch.empty(2, dtype=torch.int64, device=dev)
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, None, sizes.data_ptr(), status.data_ptr(), count, max_len, 0, 0)
+    cap = 4 * count + 64 if brk_cap is None else brk_cap
+    while True:
+        brk_pos = torch.empty(cap, dtype=torch.int64, device=dev)
+        _check(L.ez_stream_breaks_batch(block_size_limit, C.byref(b), brk_idx.data_ptr(), brk_pos.data_ptr() if cap else None, cap,
+                                        brk_total.data_ptr(), workspace.data_ptr(), _stream_ptr(stream)))
+        if brk_cap is not None:
+            # (more found than brk_cap: nothing was written, and the caller sees that in brk_idx[-1] > brk_cap)
+            break
+        written, found = (int(v) for v in brk_total.cpu())
+        if found <= cap:
+            brk_pos = brk_pos[:written]
+            break
+        cap = found
+    return brk_idx, brk_pos, sizes, status
 
 
 def decompress_batch_sized(comp, comp_off, block_size_limit: int = 0, stream=None):

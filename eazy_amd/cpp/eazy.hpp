@@ -784,6 +784,21 @@ inline Err DecompressBatchSegmented(int64_t block_size_limit, const ez_batch &b,
     if (st == EZ_EINVAL) throw std::invalid_argument("eazy: DecompressBatchSegmented: in_off, out_off and out_size are required");
     return (Err)st;
 }
+// ez_stream_breaks_batch (K2b): every stream's Break positions (Writer.WriteBreak's markers, which the
+// batch decoders skip) without decoding.  Stream s owns brk_pos[brk_idx[s] .. brk_idx[s+1]): the bytes a
+// Reader has produced at each ErrBreak before the stream's first error, which are offsets into its
+// decoded output; brk_total = {positions written, Breaks found}: more found than brk_cap writes none,
+// and the caller asks again with room.  b.out_size and b.status (may be null) get what
+// DecompressedSizeBatch reports; b.out and b.out_off are not used.  Device arrays: brk_idx[count+1],
+// brk_pos[brk_cap] (may be null with brk_cap == 0), brk_total[2], workspace of
+// ez_breaks_workspace(count) bytes (null: the exact decoder alone, the same results); b.max_len is the
+// longest INPUT stream (0: unknown).  Asynchronous on hip_stream.
+inline Err StreamBreaksBatch(int64_t block_size_limit, const ez_batch &b, uint64_t *brk_idx, uint64_t *brk_pos, uint64_t brk_cap,
+                             uint64_t *brk_total, void *workspace, void *hip_stream) {
+    const int st = ez_stream_breaks_batch(block_size_limit, &b, brk_idx, brk_pos, brk_cap, brk_total, workspace, hip_stream);
+    if (st == EZ_EINVAL) throw std::invalid_argument("eazy: StreamBreaksBatch: out_size, brk_idx and brk_total are required, and brk_pos with brk_cap != 0");
+    return (Err)st;
+}
 // ez_select_segments_route: the route of later segment queries ('p' the parts route at any stream
 // length, given b.in_bytes; 'v' never the parts route; 0 automatic).  Tests and A/B only.
 inline Err SelectSegmentsRoute(int kind) {

@@ -405,6 +405,30 @@ extern "C" int ez_segments_last(uint64_t counts[3]) {
     return EZ_OK;
 }
 
+// ---- K2b: the Break index (ez_decompress_brk.hip)
+
+extern "C" size_t ez_breaks_workspace(uint64_t count) { return (size_t)ez::breaks_workspace_bytes(count); }
+
+extern "C" int ez_stream_breaks_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *brk_idx, uint64_t *brk_pos, uint64_t brk_cap,
+                                      uint64_t *brk_total, void *workspace, void *hip_stream) {
+    if (!b || !b->out_size || !brk_idx || !brk_total || (!brk_pos && brk_cap != 0)) return EZ_EINVAL;
+    if (b->count != 0 && (!b->in || !b->in_off)) return EZ_EINVAL;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    ez::BrkArgs a{};
+    a.in = b->in;
+    a.in_off = b->in_off;
+    a.out_size = b->out_size;
+    a.status = b->status;
+    a.count = b->count;
+    a.block_size_limit = block_size_limit;
+    a.brk_idx = brk_idx;
+    a.brk_pos = brk_pos;
+    a.brk_cap = brk_cap;
+    a.brk_total = brk_total;
+    EZ_HIP(ez::launch_breaks(a, b->max_len, workspace, (hipStream_t)hip_stream));
+    return EZ_OK;
+}
+
 // Frees the device scratch the batch calls keep between calls (no reference counterpart; like a
 // caching allocator's empty_cache): the K1 / K1c scratch and K2j workspaces per (device, HIP stream),
 // the multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace,

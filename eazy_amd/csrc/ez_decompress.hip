@@ -189,8 +189,13 @@ __device__ int d_read_loop(Dec &d, int64_t plen, int64_t *i, int64_t *nout, bool
 __global__ __launch_bounds__(64) void k2_decompress(DecompressArgs A) {
     const int lane = lane_id();
     const uint64_t todo = A.slow ? (uint64_t)A.slow[0] : A.count;
+    if (A.brk_out && A.brk_gate[0] == 0) return;  // (K2b's fill: no Break, or more than there is room for)
     for (uint64_t k = blockIdx.x; k < todo; k += gridDim.x) {
         const uint64_t s = A.slow ? (uint64_t)A.slow[1 + k] : k;
+        // K2b's per-stream Break mode: the stream's Breaks are counted (brk_n), or written in place (brk_out)
+        const uint64_t brk0 = A.brk_out ? A.brk_base[s] : 0, brk_room = A.brk_out ? A.brk_base[s + 1] - brk0 : 0;
+        if (A.brk_out && brk_room == 0) continue;
+        uint64_t nbrk = 0;
         Dec d;
         d.b = A.in + A.in_off[s];
         d.nb = (int64_t)(A.in_off[s + 1] - A.in_off[s]);
@@ -246,6 +251,10 @@ __global__ __launch_bounds__(64) void k2_decompress(DecompressArgs A) {
                 const uint64_t at = A.breaks[0]++;
                 if (at < A.breaks_cap) A.breaks[1 + at] = (uint64_t)total;
             }
+            if (err == EZ_EBREAK && (A.brk_n || A.brk_out)) {
+                if (lane == 0 && nbrk < brk_room) A.brk_out[brk0 + nbrk] = (uint64_t)total;
+                nbrk++;
+            }
             if (err == EZ_OK || err == EZ_EBREAK) continue;
             if (err == EZ_ESHORTBUF) err = (d.state != 0 || i < d.nb) ? EZ_EUNEXPECTEDEOF : EZ_OK;
             break;
@@ -253,6 +262,7 @@ __global__ __launch_bounds__(64) void k2_decompress(DecompressArgs A) {
         if (lane == 0) {
             A.out_size[s] = (uint64_t)total;
             if (A.status) A.status[s] = err;
+            if (A.brk_n) A.brk_n[s] = nbrk;
             if (A.end_state) {
                 A.end_state[0] = d.bs;
                 A.end_state[1] = d.pos;
@@ -359,6 +369,13 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
     a.slow = second;
     const uint64_t exact_grid = a.count < 4096 ? a.count : 4096;
     hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_exact_dry(const DecompressArgs &a, hipStream_t st) {
+    if (a.count == 0) return hipSuccess;
+    const uint64_t most = a.slow ? 4096 : (1u << 30);
+    hipLaunchKernelGGL(k2_decompress, dim3((unsigned)(a.count < most ? a.count : most)), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 

@@ -152,6 +152,16 @@ struct DecompressArgs {
     // small), else only the streams s without parts (size_base[s] == size_base[s + 1])
     const uint32_t *size_gate;
     const uint32_t *size_base;
+    // batch, the Break index (K2b, ez_stream_breaks_batch), optional, the exact decoder run dry: the
+    // count mode, brk_n[s] = the ErrBreaks of stream s before its first error; the fill mode (brk_out
+    // set), Break k of stream s goes to brk_out[brk_base[s] + k], only the streams that own Breaks
+    // (brk_base[s] != brk_base[s + 1]) are read, and nothing is done where the device word
+    // brk_gate[0] is 0.  Null: the decoder does what it does without them (breaks above is the
+    // Reader handles' one-stream counter, which these leave alone)
+    uint64_t *brk_n;
+    const uint64_t *brk_base;
+    uint64_t *brk_out;
+    const uint64_t *brk_gate;
 };
 
 // a fast path hands stream s over: appended to the slow list (one lane per stream calls this)
@@ -326,6 +336,29 @@ uint32_t *size_segs_counters(uint32_t *slow, uint64_t count);
 // parts: the parts route's stage may take the listed streams that have parts (given a.in_bytes)
 hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream_t s, bool parts);
 hipError_t segments_last(uint64_t counts[3]);  // of the last segmented decode: segments, handed over, query retries
+// K2b, the Break index (ez_decompress_brk.hip): stream s owns brk_pos[brk_idx[s] .. brk_idx[s+1]), the
+// output positions of its Breaks; brk_total = {positions written, Breaks found}: more found than
+// brk_cap writes none
+struct BrkArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;   // count+1
+    uint64_t *out_size;       // count
+    int32_t *status;          // count or nullptr
+    uint64_t count;
+    int64_t block_size_limit;
+    uint64_t *brk_idx;        // count+1
+    uint64_t *brk_pos;        // brk_cap (may be null with brk_cap == 0)
+    uint64_t brk_cap;
+    uint64_t *brk_total;      // 2
+    uint32_t *list;           // the workspace's hand-over list, [0] = its length, and the per-stream
+    uint32_t *handed;         // "handed over" words (set by the launcher)
+};
+uint64_t breaks_workspace_bytes(uint64_t count);
+// max_len: the caller's hint, the longest input stream (0 = unknown), which picks the chunk (size_chunk);
+// workspace null: the exact decoder alone
+hipError_t launch_breaks(const BrkArgs &a, uint64_t max_len, void *workspace, hipStream_t s);
+// the exact decoder run dry (a.dry) over a.slow's list, or over the whole batch without one
+hipError_t launch_exact_dry(const DecompressArgs &a, hipStream_t s);
 bool lds_exchange_in_lane_order();  // the LDS property K1s-T32 relies on (checked once, ez_k1_probe.hip)
 bool lds_mskor_in_lane_order();     // the LDS property k1_lean's one-atomic visit relies on (checked once)
 hipError_t launch_pack(const uint8_t *slots, const uint64_t *slot_off, const uint64_t *sizes, uint64_t count,

@@ -410,6 +410,125 @@ func DecompressBatchSegmented(streams [][]byte, caps []uint64, blockSizeLimit in
 	return res, errs, nil
 }
 
+// StreamBreaksBatch lists the Breaks of independent streams on the GPU without decoding them
+// (ez_stream_breaks_batch, K2b): breaks[k] holds, for every ErrBreak that NewReaderBytes(streams[k])
+// read to EOF returns before its first error, the bytes the Reader has produced by then, in order:
+// offsets into the stream's decoded output (what DecompressBatchSegmented returns for it), so that
+// out[breaks[k][j-1]:breaks[k][j]] is message j.  sizes[k] is the decoded length and errs[k] the
+// Reader's error, as the size query reports them.  The streams are staged into device memory and the
+// calls run on the null stream; where the Breaks found exceed the room of the first call, the query
+// runs once more with room.  Every HIP call's result is checked before anything is used.
+func StreamBreaksBatch(streams [][]byte, blockSizeLimit int) (breaks [][]uint64, sizes []uint64, errs []error, err error) {
+	count := len(streams)
+	if count == 0 {
+		return nil, nil, nil, nil
+	}
+	inOff := make([]uint64, count+1)
+	maxLen := 0
+	for k, s := range streams {
+		inOff[k+1] = inOff[k] + uint64(len(s))
+		if len(s) > maxLen {
+			maxLen = len(s)
+		}
+	}
+	host := make([]byte, 0, inOff[count])
+	for _, s := range streams {
+		host = append(host, s...)
+	}
+	var dIn, dInOff, dSize, dStatus, dIdx, dPos, dTotal, dWork unsafe.Pointer
+	defer func() {
+		for _, p := range []unsafe.Pointer{dIn, dInOff, dSize, dStatus, dIdx, dPos, dTotal, dWork} {
+			if p != nil {
+				C.hipFree(p)
+			}
+		}
+	}()
+	// every HIP call's result is checked: a failed copy must never hand back stale words as success
+	hip := func(r C.hipError_t) error {
+		if r != C.hipSuccess {
+			return ErrDevice
+		}
+		return nil
+	}
+	for _, a := range []struct {
+		p *unsafe.Pointer
+		n uint64
+	}{{&dIn, inOff[count]}, {&dInOff, 8 * uint64(count+1)}, {&dSize, 8 * uint64(count)}, {&dStatus, 4 * uint64(count)},
+		{&dIdx, 8 * uint64(count+1)}, {&dTotal, 16}, {&dWork, uint64(C.ez_breaks_workspace(C.uint64_t(count)))}} {
+		if err := hip(C.hipMalloc(a.p, C.size_t(a.n+16))); err != nil {
+			return nil, nil, nil, err
+		}
+	}
+	if len(host) > 0 {
+		if err := hip(C.hipMemcpy(dIn, unsafe.Pointer(&host[0]), C.size_t(len(host)), C.hipMemcpyHostToDevice)); err != nil {
+			return nil, nil, nil, err
+		}
+	}
+	if err := hip(C.hipMemcpy(dInOff, unsafe.Pointer(&inOff[0]), C.size_t(8*(count+1)), C.hipMemcpyHostToDevice)); err != nil {
+		return nil, nil, nil, err
+	}
+	b := C.ez_batch{
+		in: (*C.uint8_t)(dIn), in_off: (*C.uint64_t)(dInOff), out_size: (*C.uint64_t)(dSize), status: (*C.int32_t)(dStatus),
+		count: C.uint64_t(count), max_len: C.uint64_t(maxLen),
+	}
+	room := uint64(4*count + 64)
+	var total [2]uint64
+	for try := 0; ; try++ {
+		if err := hip(C.hipMalloc(&dPos, C.size_t(8*room+16))); err != nil {
+			return nil, nil, nil, err
+		}
+		if st := C.ez_stream_breaks_batch(C.int64_t(blockSizeLimit), &b, (*C.uint64_t)(dIdx), (*C.uint64_t)(dPos), C.uint64_t(room),
+			(*C.uint64_t)(dTotal), dWork, nil); st != C.EZ_OK {
+			return nil, nil, nil, toErr(st, 0)
+		}
+		// (hipMemcpy to host waits for the query's kernels on the null stream, and reports their faults)
+		if err := hip(C.hipMemcpy(unsafe.Pointer(&total[0]), dTotal, 16, C.hipMemcpyDeviceToHost)); err != nil {
+			return nil, nil, nil, err
+		}
+		if total[1] <= room {
+			break
+		}
+		if try != 0 {
+			return nil, nil, nil, ErrDevice // (never: the second call has the room the first one asked for)
+		}
+		if err := hip(C.hipFree(dPos)); err != nil {
+			return nil, nil, nil, err
+		}
+		dPos = nil
+		room = total[1]
+	}
+	idx := make([]uint64, count+1)
+	pos := make([]uint64, total[0]+1)
+	sizes = make([]uint64, count)
+	status := make([]int32, count)
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&idx[0]), dIdx, C.size_t(8*(count+1)), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, nil, err
+	}
+	if total[0] > 0 {
+		if err := hip(C.hipMemcpy(unsafe.Pointer(&pos[0]), dPos, C.size_t(8*total[0]), C.hipMemcpyDeviceToHost)); err != nil {
+			return nil, nil, nil, err
+		}
+	}
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&sizes[0]), dSize, C.size_t(8*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, nil, err
+	}
+	if err := hip(C.hipMemcpy(unsafe.Pointer(&status[0]), dStatus, C.size_t(4*count), C.hipMemcpyDeviceToHost)); err != nil {
+		return nil, nil, nil, err
+	}
+	breaks = make([][]uint64, count)
+	errs = make([]error, count)
+	for k := range streams {
+		if idx[k] > idx[k+1] || idx[k+1] > total[0] {
+			return nil, nil, nil, ErrDevice // (never: brk_idx is an exclusive scan that ends at the Breaks found)
+		}
+		breaks[k] = pos[idx[k]:idx[k+1]:idx[k+1]]
+		if status[k] != 0 {
+			errs[k] = toErr(C.int(status[k]), 0)
+		}
+	}
+	return breaks, sizes, errs, nil
+}
+
 // SelectSegmentsRoute sets the route of later segment queries (ez_select_segments_route): 'p' the
 // parts route at any stream length, 'v' never the parts route, 0 automatic.  Tests and A/B only.
 func SelectSegmentsRoute(kind int) error {

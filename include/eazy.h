@@ -422,6 +422,40 @@ int ez_decompress_batch_segmented(int64_t block_size_limit, const ez_batch *b, v
  * counts[1] back from the library's scratch (0 once ez_release_cached freed it). */
 int ez_segments_last(uint64_t counts[3]);
 
+/* K2b: the Break index.  Writer.WriteBreak (writer.go:352-366) writes a two-byte marker that separates
+ * chunks of data in one stream; Reader.Read returns ErrBreak there and stays valid (reader.go:66-75,
+ * :312-313).  The batch decoders above skip the markers; this query lists them, for every stream of a
+ * batch, without decoding: a stream's Breaks are the ErrBreaks NewReaderBytes(in_s) read to EOF returns
+ * before its first error, in order, and a Break's position is the number of bytes the Reader has
+ * produced when the ErrBreak comes back: the offset into the slot ez_decompress_batch fills, relative
+ * to the slot's start.  Positions do not decrease; two Breaks with no output between them give the
+ * same position twice (an empty message); a Break before any output has position 0; a stream that
+ * holds MetaResets after output counts its output across all of them, as the slot does; nothing after
+ * the first error is listed.
+ * Stream s owns brk_pos[brk_idx[s] .. brk_idx[s+1]) (brk_idx[count+1], the exclusive scan of the
+ * streams' Break counts: always written in full, always the true counts).  brk_total[1] = the Breaks
+ * found (= brk_idx[count]), brk_total[0] = the positions written: all of them, or, where the Breaks
+ * found exceed brk_cap, none (no entry of brk_pos is written), so that a caller can retry with room.
+ * brk_pos may be NULL when brk_cap is 0.  out_size[s] and status[s] are exactly what
+ * ez_decompressed_size_batch reports.
+ * Uses b->in, in_off, out_size (required), status (may be NULL), count and max_len (host hint: the
+ * longest INPUT stream in bytes, 0 = unknown; it picks the chunk size as ez_decompressed_size_chunk
+ * says and nothing else: any value gives the same arrays); out, out_off, in_bytes and out_bytes are
+ * ignored.  workspace >= ez_breaks_workspace(count) device bytes enables the fast walk (a wave per
+ * stream over the true token chain, once to count and, for the streams that own Breaks, once more to
+ * write; streams it cannot take go whole to the exact decoder run dry); NULL = the exact decoder alone,
+ * with the same results.  The workspace's contents on entry are ignored and nothing is written past
+ * its size.  All pointers are device pointers.  Asynchronous on hip_stream; never waits for the stream.
+ * Memory touched: reads in[0 .. in_off[count]) as ez_decompress_batch does; writes only
+ * out_size[0..count), status[0..count), brk_idx[0..count], brk_pos[0..brk_total[0]), brk_total[0..1]
+ * and the workspace.  EZ_EINVAL for a NULL b, out_size, brk_idx or brk_total, and for a NULL brk_pos
+ * with brk_cap != 0; count == 0 writes brk_idx[0] = 0 and brk_total = {0, 0} and returns EZ_OK.
+ * Held by tests/test_k2_breaks.py, tests/test_capi_breaks.py, tests/test_gpu_breaks.py and
+ * tests/test_cpp_breaks.py. */
+size_t ez_breaks_workspace(uint64_t count);
+int ez_stream_breaks_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *brk_idx, uint64_t *brk_pos, uint64_t brk_cap,
+                           uint64_t *brk_total, void *workspace, void *hip_stream);
+
 /* ---- host-memory batches over several devices (SURVEY §8b device_or_all) ----
  * Streams share no state (writer.go:40-45, reader.go:17-40), so a batch splits into contiguous
  * whole-stream shards, balanced by bytes, one per entry of `devices` (ndev entries; NULL or 0 =
