@@ -226,7 +226,9 @@ typedef struct {
 
 #define EZ_F_NO_MAGIC 0x1 /* compress: AppendMagic = false */
 
-/* K1: compress every stream of b into its slot (slot >= ez_compress_bound(n)). */
+/* K1: compress every stream of b into its slot (slot >= ez_compress_bound(n)).  Held by
+ * tests/test_gpu_k1_edges.py and tests/test_gpu_k1_hints.py; at offsets past 2^31 and 2^32 and on
+ * batches larger than 4 GiB by tests/test_gpu_high_offsets.py. */
 int ez_compress_batch(int64_t block, int64_t htable, int flags, const ez_batch *b, void *hip_stream);
 /* K1 for streams that each receive several Writes (Writer.Write writer.go:206
  * called k times on one NewWriter, FlushThreshold 0: the slot holds what the
@@ -270,7 +272,9 @@ int ez_pack_batch(const uint8_t *slots, const uint64_t *slot_off, const uint64_t
  * out_size[s] on untouched; a stream with an error may leave part of its slot overwritten (a fast
  * decoder's output before the hand-over), never a byte outside it.  A fast decoder takes only
  * slots of at least 16 bytes and batches of at least 16 input bytes; the others go to the exact
- * decoder.  Held by tests/test_gpu_k2r.py, test_gpu_k2t.py and test_gpu_k2j.py.
+ * decoder.  Held by tests/test_gpu_k2r.py, test_gpu_k2t.py and test_gpu_k2j.py; at offsets past
+ * 2^31 and 2^32, at slots of 2^30 bytes and more and on batches larger than 4 GiB by
+ * tests/test_gpu_high_offsets.py.
  * The workspace's contents on entry are ignored: it need not be cleared, it may hold what any
  * earlier call left there (this call's, the size query's, another batch's), and nothing is written
  * past ez_decompress_workspace(count) bytes.  out_size[s] and status[s] are written for every
@@ -299,8 +303,8 @@ int ez_decompress_batch(int64_t block_size_limit, const ez_batch *b, void *works
  * if it cannot be had the call takes the wave route).  Asynchronous on hip_stream; never waits for the stream.  Reads in[0 .. in_off[count]) as
  * ez_decompress_batch does; writes only out_size[0..count), status[0..count) and the workspace.
  * Sizes are 64-bit throughout: an output over 4 GiB is reported, not clamped.
- * Held by tests/test_gpu_k2z.py, tests/test_k2_size.py, tests/test_gpu_k2z_parts.py and
- * tests/test_k2_size_parts.py. */
+ * Held by tests/test_gpu_k2z.py, tests/test_k2_size.py, tests/test_gpu_k2z_parts.py,
+ * tests/test_k2_size_parts.py and (offsets past 2^31 and 2^32) tests/test_gpu_high_offsets.py. */
 int ez_decompressed_size_batch(int64_t block_size_limit, const ez_batch *b, void *workspace, void *hip_stream);
 /* Introspection (tests, tuning): the chunk bytes the fast kernel takes for a max_len hint (host function). */
 int ez_decompressed_size_chunk(uint64_t max_len);
@@ -374,8 +378,8 @@ int ez_decompressed_size_segs_last(const void *workspace, uint64_t count, uint64
  * seg_idx[0 .. count], seg_in and seg_out[0 .. seg_total[0]], seg_total[0 .. 1] and the workspace.
  * The workspace's contents on entry are ignored: it need not be cleared, and nothing is written past
  * ez_segments_workspace(count) bytes; the parts route's scratch is the library's own.
- * Held by tests/test_k2_segments.py, tests/test_gpu_segments.py, tests/test_k2_segs_parts.py and
- * tests/test_gpu_segments_parts.py. */
+ * Held by tests/test_k2_segments.py, tests/test_gpu_segments.py, tests/test_k2_segs_parts.py,
+ * tests/test_gpu_segments_parts.py and (offsets past 2^31 and 2^32) tests/test_gpu_high_offsets.py. */
 size_t ez_segments_workspace(uint64_t count);
 int ez_stream_segments_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *seg_idx, uint64_t *seg_in, uint64_t *seg_out,
                              uint64_t seg_cap, uint64_t *seg_total, void *workspace, void *hip_stream);
@@ -450,8 +454,8 @@ int ez_segments_last(uint64_t counts[3]);
  * out_size[0..count), status[0..count), brk_idx[0..count], brk_pos[0..brk_total[0]), brk_total[0..1]
  * and the workspace.  EZ_EINVAL for a NULL b, out_size, brk_idx or brk_total, and for a NULL brk_pos
  * with brk_cap != 0; count == 0 writes brk_idx[0] = 0 and brk_total = {0, 0} and returns EZ_OK.
- * Held by tests/test_k2_breaks.py, tests/test_capi_breaks.py, tests/test_gpu_breaks.py and
- * tests/test_cpp_breaks.py. */
+ * Held by tests/test_k2_breaks.py, tests/test_capi_breaks.py, tests/test_gpu_breaks.py,
+ * tests/test_cpp_breaks.py and (offsets past 2^31 and 2^32) tests/test_gpu_high_offsets.py. */
 size_t ez_breaks_workspace(uint64_t count);
 int ez_stream_breaks_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *brk_idx, uint64_t *brk_pos, uint64_t brk_cap,
                            uint64_t *brk_total, void *workspace, void *hip_stream);
