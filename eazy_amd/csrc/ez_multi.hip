@@ -12,25 +12,11 @@
 
 #include "ez_format.h"
 #include "ez_host.h"
+#include "ez_multi_shards.h"
 
 using namespace ez;
 
 namespace {
-// Contiguous whole-stream shards of a batch, balanced by bytes: shard k is streams [first[k],
-// first[k+1]) with first[k] the first stream starting at or after k / nshard of the batch's bytes.
-std::vector<uint64_t> shard_bounds(const uint64_t *off, uint64_t count, int nshard) {
-    std::vector<uint64_t> first((size_t)nshard + 1, count);
-    first[0] = 0;
-    const uint64_t total = off[count] - off[0];
-    uint64_t s = 0;
-    for (int k = 1; k < nshard; k++) {
-        const uint64_t target = off[0] + (uint64_t)((unsigned __int128)total * (uint64_t)k / (uint64_t)nshard);
-        while (s < count && off[s] < target) s++;
-        first[(size_t)k] = s;
-    }
-    return first;
-}
-
 int resolve_devices(const int *devices, int ndev, std::vector<int> &out) {
     const int have = device_count();
     if (have <= 0) return EZ_EDEVICE;
@@ -149,18 +135,8 @@ Shards make_shards(const uint64_t *in_off, uint64_t count, const std::vector<int
     return sh;
 }
 
-// a shard's c + 1 offsets, from its first stream's
-std::vector<uint64_t> rebased(const uint64_t *off, const Shard &x) {
-    std::vector<uint64_t> v(x.count + 1);
-    for (uint64_t t = 0; t <= x.count; t++) v[t] = off[x.first + t] - off[x.first];
-    return v;
-}
-// the largest stream (or slot) between them
-uint64_t max_span(const std::vector<uint64_t> &off) {
-    uint64_t mx = 0;
-    for (size_t t = 1; t < off.size(); t++) mx = off[t] - off[t - 1] > mx ? off[t] - off[t - 1] : mx;
-    return mx;
-}
+// a shard's c + 1 offsets, from its first stream's (ez_multi_shards.h)
+std::vector<uint64_t> rebased(const uint64_t *off, const Shard &x) { return ez::rebased(off, x.first, x.count); }
 
 // the per-shard device intervals of the last multi-device call (ez_multi_last_shards)
 struct ShardTime {
@@ -242,6 +218,7 @@ extern "C" int ez_compress_batch_multi(int64_t block, int64_t htable, int flags,
                                        uint64_t count, const int *devices, int ndev, uint8_t *packed, uint64_t packed_cap,
                                        uint64_t *packed_off, int32_t *status) {
     if (!valid_writer_sizes(block, htable) || !in_off || !packed_off) return EZ_EINVAL;
+    if (!offsets_ascend(in_off, count)) return EZ_EINVAL;  // (nothing written, packed_off[0] neither)
     std::vector<int> devs;
     int e = resolve_devices(devices, ndev, devs);
     if (e != EZ_OK) return e;
@@ -305,6 +282,7 @@ extern "C" int ez_decompress_batch_multi(int64_t block_size_limit, const uint8_t
                                          const int *devices, int ndev, uint8_t *out, const uint64_t *out_off, uint64_t *out_size,
                                          int32_t *status) {
     if (!in_off || !out_off || !out_size) return EZ_EINVAL;
+    if (!offsets_ascend(in_off, count) || !offsets_ascend(out_off, count)) return EZ_EINVAL;
     std::vector<int> devs;
     int e = resolve_devices(devices, ndev, devs);
     if (e != EZ_OK) return e;
@@ -343,6 +321,7 @@ extern "C" int ez_decompress_batch_multi(int64_t block_size_limit, const uint8_t
 extern "C" int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in, const uint64_t *in_off, uint64_t count,
                                                 const int *devices, int ndev, uint64_t *out_size, int32_t *status) {
     if (!in_off || !out_size) return EZ_EINVAL;
+    if (!offsets_ascend(in_off, count)) return EZ_EINVAL;
     std::vector<int> devs;
     int e = resolve_devices(devices, ndev, devs);
     if (e != EZ_OK) return e;

@@ -466,12 +466,18 @@ int ez_stream_breaks_batch(int64_t block_size_limit, const ez_batch *b, uint64_t
  * every visible device; an entry may repeat: two shards on one device, each on its own HIP
  * stream); each shard runs on its own host thread: upload, the batch kernels, download.  All
  * pointers are HOST pointers; the calls return when the output is in host memory.
+ * Shard k begins with the first stream that starts at or after k / ndev of the batch's bytes
+ * (eazy_amd/csrc/ez_multi_shards.h, held on the host by tests/test_multi_shards.py); a shard may be
+ * empty, and each shard takes its own route from its own longest stream and byte counts.
  *
  * Compress: stream s = in[in_off[s] .. in_off[s+1]) as one Write to a fresh NewWriter(block,
  * htable); packed gets the streams' outputs back to back, packed_off[count+1] their offsets
  * (a host exclusive scan of the shards' packed sizes), status[count] (may be NULL) EZ_* per
  * stream.  packed_cap < packed_off[count] -> EZ_ENOSPC with packed_off filled, packed untouched
- * (sum of ez_compress_bound(n) always suffices). */
+ * (sum of ez_compress_bound(n) always suffices).  EZ_EINVAL for invalid sizes, a NULL in_off or
+ * packed_off, an in_off that decreases anywhere (all checked before any device use) or a device
+ * entry that does not exist: nothing is written then, packed_off[0] neither.
+ * Held by tests/test_gpu_multi_edges.py (the oracle at every shard edge) and tests/test_gpu_batch.py. */
 int ez_compress_batch_multi(int64_t block, int64_t htable, int flags, const uint8_t *in, const uint64_t *in_off, uint64_t count,
                             const int *devices, int ndev, uint8_t *packed, uint64_t packed_cap, uint64_t *packed_off,
                             int32_t *status);
@@ -479,7 +485,11 @@ int ez_compress_batch_multi(int64_t block, int64_t htable, int flags, const uint
  * metas skipped) into out[out_off[s] .. out_off[s+1]); out_size[count] bytes produced,
  * status[count] (may be NULL) EZ_OK or the first error, as ez_decompress_batch.  On this host
  * path the bytes of a slot past out_size[s] are unspecified (each shard's whole device range is
- * copied down, whatever its pooled buffer held). */
+ * copied down, whatever its pooled buffer held).  EZ_EINVAL for a NULL in_off, out_off or out_size,
+ * an in_off or out_off that decreases anywhere (all checked before any device use) or a device entry
+ * that does not exist: nothing is written then.
+ * Held by tests/test_gpu_multi_edges.py (the oracle at every shard edge), tests/test_gpu_batch.py and
+ * tests/test_gpu_size_multi.py. */
 int ez_decompress_batch_multi(int64_t block_size_limit, const uint8_t *in, const uint64_t *in_off, uint64_t count,
                               const int *devices, int ndev, uint8_t *out, const uint64_t *out_off, uint64_t *out_size,
                               int32_t *status);
@@ -487,8 +497,9 @@ int ez_decompress_batch_multi(int64_t block_size_limit, const uint8_t *in, const
  * large enough, without decoding and without an output (ez_decompressed_size_batch on every shard,
  * with each shard's max_len and in_bytes hints): out_size[count] and status[count] (may be NULL).
  * A caller that does not know its decoded lengths lays its slots out from out_size (a host prefix
- * sum) and then calls ez_decompress_batch_multi.  EZ_EINVAL for NULL in_off or out_size (checked
- * before any device use); count == 0 returns EZ_OK. */
+ * sum) and then calls ez_decompress_batch_multi.  EZ_EINVAL for NULL in_off or out_size or an in_off
+ * that decreases anywhere (checked before any device use, nothing written); count == 0 returns EZ_OK.
+ * Held by tests/test_gpu_multi_edges.py (the oracle at every shard edge) and tests/test_gpu_size_multi.py. */
 int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in, const uint64_t *in_off, uint64_t count,
                                      const int *devices, int ndev, uint64_t *out_size, int32_t *status);
 
@@ -515,7 +526,9 @@ int ez_release_cached(int device);
 int ez_fill_cached(int device, int byte, uint64_t *bytes);
 /* Introspection (tests, measurement): the shards of the last ez_*_batch_multi call in this process
  * (returns their number; up to cap entries filled, any pointer may be NULL): each shard's device and
- * its device interval (upload to download) in ms from the earliest shard start on that device. */
+ * its device interval (upload to download) in ms from the earliest shard start on that device.
+ * Empty shards are not counted; with cap below the number, the number is still returned.
+ * Held by tests/test_gpu_multi_edges.py. */
 int ez_multi_last_shards(int *dev, double *t0_ms, double *t1_ms, int cap);
 
 /* Introspection (no reference counterpart): the K1 kernel a batch of `count`
