@@ -36,10 +36,28 @@ namespace k1 {
 // a match record, 8 bytes: lit_end | copy length << 20 | distance << 40 | force << 60
 // (positions < 2^20: streams <= kMaxT32); force: the literal is emitted even when
 // empty (writeRunlen :480)
-__host__ __device__ __forceinline__ uint64_t rec_pack(int32_t lit_end, int32_t clen, int32_t dist, bool force) {
+__host__ __device__ __forceinline__ constexpr uint64_t rec_pack(int32_t lit_end, int32_t clen, int32_t dist, bool force) {
     return (uint64_t)(uint32_t)lit_end | ((uint64_t)(uint32_t)clen << 20) | ((uint64_t)(uint32_t)dist << 40) | ((uint64_t)force << 60);
 }
-constexpr int64_t kMaxT16 = 65536;   // T16 positions fit 16 bits (a stream's visited positions are < n - 3)
+// the same record as its two dwords (k1_lean's windows build it this way: no 64-bit shift or or):
+// lo = lit_end | clen << 20 (the length's low 12 bits), hi = clen >> 12 | dist << 8 | force << 28
+struct Rec32 {
+    uint32_t lo, hi;
+};
+__host__ __device__ constexpr Rec32 rec_pack32(int32_t lit_end, int32_t clen, int32_t dist, bool force) {
+    return Rec32{(uint32_t)lit_end | ((uint32_t)clen << 20), ((uint32_t)clen >> 12) | ((uint32_t)dist << 8) | ((uint32_t)force << 28)};
+}
+constexpr bool rec_pack32_same(int32_t lit_end, int32_t clen, int32_t dist, bool force) {
+    const Rec32 r = rec_pack32(lit_end, clen, dist, force);
+    return (((uint64_t)r.hi << 32) | r.lo) == rec_pack(lit_end, clen, dist, force);
+}
+// every field at its ends and across the dword seam (bit 12 of the length), positions < 2^20
+static_assert(rec_pack32_same(0, 0, 0, false) && rec_pack32_same((1 << 20) - 1, (1 << 20) - 1, (1 << 20) - 1, true) &&
+                  rec_pack32_same(0, 4095, 1, false) && rec_pack32_same(1, 4096, 0, true) && rec_pack32_same(64, 4097, 4096, false) &&
+                  rec_pack32_same(12345, 65472, 32768, true) && rec_pack32_same((1 << 20) - 1, 0, 0, false) &&
+                  rec_pack32_same(0, (1 << 20) - 1, 0, false) && rec_pack32_same(0, 0, (1 << 20) - 1, false) && rec_pack32_same(0, 0, 0, true),
+              "rec_pack32 is rec_pack's two halves");
+constexpr int64_t kMaxT16 = 65536;  // T16 positions fit 16 bits (a stream's visited positions are < n - 3)
 constexpr int64_t kMaxT32 = 1 << 19; // the judgement packs the candidate into 20 bits (and 2n <= block)
 
 // record slot of stream s: s * rec_cap .. ; every match advances done by >= 6,
@@ -132,6 +150,7 @@ __device__ __forceinline__ void gext(const SRC &P, bool runf, bool runb, int g, 
 // Aligned loads of stream bytes in the global address space (k1_lean's windows and candidates,
 // K1L's candidates inside the batch): plain global_load instructions, not flat ones, which would
 // also count against the LDS counter and wait on the ds_bpermute traffic
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) uint32_t *gu32p;
 typedef const __attribute__((address_space(1))) u32x4 *gu128p;

@@ -167,6 +167,30 @@ __device__ __forceinline__ void bytes48(const LeanIn &L, const uint8_t *p, int32
     c2 = V16{(uint64_t)b[8] | ((uint64_t)b[9] << 32), (uint64_t)b[10] | ((uint64_t)b[11] << 32)};
 }
 
+// The wave's lane mask of one compare.  A ballot of a single compare is that compare's own SGPR
+// result; a ballot of a compound bool is first made a VGPR 0/1 (v_cndmask) and compared again
+// (v_cmp_ne), two VALU per window each.  So a compound condition is formed from its component
+// compares' masks on the scalar side (s_and_b64 / s_or_b64): lanes(a, b) is the mask of a && b.
+__device__ __forceinline__ uint64_t lanes(bool c) { return __builtin_amdgcn_ballot_w64(c); }
+template <class... B>
+__device__ __forceinline__ uint64_t lanes(bool c, B... more) { return lanes(c) & lanes(more...); }
+
+// v + 1 in the lanes of mask m: one add with carry-in (a select of 0 / 1 and an add otherwise)
+__device__ __forceinline__ int32_t add_lanes(int32_t v, uint64_t m) {
+    asm("v_addc_co_u32_e64 %0, %1, 0, %0, %1" : "+v"(v), "+s"(m));
+    return v;
+}
+
+// bit 0: s_setprio 3 on the chain up to the candidate loads; bit 2: the i+1 insert by lane a+1
+// (EZ_K1S_NEXT1=0 (A/B): by the acceptor, with its own hash).  A constant of the product build,
+// so the window carries no branch on it; experiment builds (EZ_KNOBS) take it from the launcher
+constexpr int kLeanPrio = 1 | 4;
+#ifdef EZ_KNOBS
+constexpr bool kLeanPrioKnob = true;
+#else
+constexpr bool kLeanPrioKnob = false;
+#endif
+
 #if (EZ_EXP & 65536)
 // [0..17] windows by acceptor lane (0: none); [18], [19] acceptors whose capped count had / had not room
 // left; [20] wave iterations that took the gext branch, [21] wave iterations, [22] those in which an
@@ -179,8 +203,9 @@ __device__ unsigned long long g_lean_hist[23];
 // FW: the judgement's forward cap, 24 or 40 bytes (40: 48-byte windows and candidates).
 template <int FW, int G>
 __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, uint16_t *hth, uint32_t table_words, uint32_t hsh,
-                                         uint64_t *recs, uint64_t rcap, int prio, uint8_t *edge, uint8_t *wl) {
+                                         uint64_t *recs, uint64_t rcap, int prio_knob, uint8_t *edge, uint8_t *wl) {
     constexpr int S = 64 / G;
+    const int prio = kLeanPrioKnob ? prio_knob : kLeanPrio;
     constexpr uint32_t kGMask = (1u << G) - 1;
     constexpr bool W40 = FW == 40;
     static_assert(FW == 24 || W40, "the judgement's forward cap is 24 or 40 bytes");
@@ -194,6 +219,7 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
     uint64_t s = (uint64_t)blockIdx.x * S + (uint64_t)g;
     const uint8_t *p = edge + 16;
     int32_t n = 0, i = 0, done = 0, nrec = 0;
+    int32_t nin = 0;  // n - kIn: the last i of an interior window
     int err = 0;
     bool live = false, pending = false;  // pending: the stream's size word is still to be written
     uint64_t *rec = recs;
@@ -241,6 +267,7 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
             __threadfence_block();
         }
         i = done = nrec = 0;
+        nin = n - (G + FW - 1);
         rec = recs + (pending ? s : 0) * rcap;
         wr.init(p, n, lj, live);
         // the bytes around stream position 0, the candidate of every zero table entry:
@@ -265,11 +292,13 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
     //    run's (its candidate is below x: n - cand > CAP, and cand + 8 < n);
     //  * x + 1 + 4 <= n: a window match makes its i+1 insert;
     //  * the window's bytes end at x + CAP - 1 < n.
+    // open() keeps nin = n - kIn, so the test before every window is i <= nin.
     // So the interior window has no end clamp, no liveness term and no record-room test; the exact
     // limits of a saturated count are gext's, in both forms of the window.  (The counts alone
     // would bear a bound one byte looser, since a count that reaches CAP goes to gext, which holds
     // it to the stream's end; the bound here is the one at which no lane needs that.)
     constexpr int32_t kIn = G + CAP - 1;
+    static_assert(kIn == G + FW - 1, "open()'s nin");
 
     // One window of every group of the wave.  IN: every group is interior (above); else the
     // general window, which also serves ending streams, dead groups and a full record area.
@@ -308,7 +337,11 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
         jb = jb < bl ? jb : bl;
         const bool zr = rl && c0.hi == 0 && (IN || cand + 8 < n);
         const int32_t fw = rl ? jf : (jf < done - cand ? jf : done - cand);
-        const bool acc = valid && (zr || fw + jb >= kMinCopyChunk);
+        // acc = valid && (zr || fw + jb >= kMinCopyChunk), as the wave's mask from the single compares
+        uint64_t am64 = lanes(cand >= done, cand < x, c0.hi == 0);
+        if constexpr (!IN) am64 &= lanes(cand + 8 < n);
+        am64 |= lanes(fw + jb >= kMinCopyChunk);
+        if constexpr (!IN) am64 &= lanes(live, lj < nvalid);
 
         // ---- this lane's action if it is the group's first acceptor.  ext: a count that reached
         // its cap (bit 0 forward, bit 1 backward); whether the match has room to go on past the
@@ -331,28 +364,31 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
             force = rl;
             ext = (jf == CAP ? 1 : 0) | (jb == 8 ? 2 : 0);
         }
-        const uint64_t am64 = __builtin_amdgcn_ballot_w64(acc);
-        const uint32_t am = (uint32_t)(am64 >> (G * g)) & kGMask;
-        const int a = am ? __builtin_ctz(am) : -1;
-#if (EZ_EXP & 65536)
-        if ((IN || live) && lj == 0) atomicAdd(&g_lean_hist[a + 1], 1ull);  // (experiment builds: the acceptor lane, -1 none)
-        if (lj == 0 && g == 0) atomicAdd(&g_lean_hist[21], 1ull);
-#endif
-        const bool act = (IN || live) && a >= 0;
         // the group's next position, whether the acceptor's counts reached their caps, and whether
         // it makes the i+1 insert (a window match, writer.go:315-318)
         const bool ins1 = !rl && !zr && (IN || x + 1 + 4 <= n);
+        const uint32_t am = (uint32_t)(am64 >> (G * g)) & kGMask;
+        const bool any = am != 0;
+        const int a = am ? __builtin_ctz(am) : -1;
         const int32_t pack = nx | (ext << 28) | ((int32_t)ins1 << 30);
         // (one ds_bpermute from each group's first acceptor: fewer VALU than four v_readlane + selects)
         const int32_t sel = __builtin_amdgcn_ds_bpermute(4 * (G * g + (a < 0 ? 0 : a)), pack);
+        const int a0 = any ? a : 0;  // (a lane to read from where there is no acceptor)
+#if (EZ_EXP & 65536)
+        if ((IN || live) && lj == 0) atomicAdd(&g_lean_hist[any ? a + 1 : 0], 1ull);  // (experiment builds: the acceptor lane, 0 none)
+        if (lj == 0 && g == 0) atomicAdd(&g_lean_hist[21], 1ull);
+#endif
+        uint64_t actm = lanes(any);
+        if constexpr (!IN) actm &= lanes(live);
+        const bool act = (IN || live) && any;
         int32_t nxt = sel & 0x0fffffff;
-        if (__builtin_amdgcn_ballot_w64(act && ((sel >> 28) & 3) != 0) != 0) {
+        if ((actm & lanes((sel & (3 << 28)) != 0)) != 0) {
             // rare: a count at its cap; exact lengths by the whole group (as k1_parse).  A count
             // with no room past its cap (flim <= CAP, blim <= 8) comes back from gext as it was.
             // the acceptor's candidate, capped backward count (<= 8) and branch
             const int32_t info = cand | (((zr ? cand : x) - lit) << 16) | ((int32_t)rl << 29) | ((int32_t)zr << 30);
-            const int32_t ib = bcast(info, G * g + (a < 0 ? 0 : a));
-            const int32_t xa = i + (a < 0 ? 0 : a);
+            const int32_t ib = bcast(info, G * g + a0);
+            const int32_t xa = i + a0;
             const int32_t ca = ib & 0xffff;
             const bool rla = (ib >> 29) & 1, zra = (ib >> 30) & 1;
             const int32_t e = (sel >> 28) & 3;
@@ -392,14 +428,14 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
             }
         }
         // the record, stored after the next region's load is issued (a region switch waits for every
-        // vector-memory operation before it, stores included)
+        // vector-memory operation before it, stores included), at the count as it was: nrec - 1 by
+        // then, the -1 in the store's offset
         const bool st_rec = act && lj == a;
-        const uint64_t rv = rec_pack(lit, nx - lit, dist, force);
-        const uint32_t rat = (uint32_t)nrec;
+        const Rec32 rv = rec_pack32(lit, nx - lit, dist, force);
         const bool rec_room = IN || (uint32_t)nrec < rcap32;
+        nrec = add_lanes(nrec, actm);
         if (act) {
             if (!rec_room) { err = EZ_ESTUCK; live = false; }
-            nrec++;
             i = done = nxt;
         } else if (IN || live) {
             i += nvalid;
@@ -410,7 +446,7 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
         }
         wr.advance(p, i, lj, IN || live);  // the next window's region (up to the stream's end: in bounds)
         __builtin_amdgcn_sched_barrier(0);
-        if (st_rec && rec_room) __builtin_nontemporal_store(rv, rec + rat);
+        if (st_rec && rec_room) __builtin_nontemporal_store(u32x2{rv.lo, rv.hi}, (u32x2 *)(rec + (uint32_t)nrec - 1));
     };
 
     for (;;) {
@@ -432,10 +468,10 @@ __device__ __forceinline__ void lean_run(const CompressArgs &A, int lj, int g, u
         // test of it to this outer loop: every window advances its group's i or, where a match
         // ends at i itself, done up to i (done <= i <= n), so the loop ends within 2n windows
         // whatever the budget says, and a wrong parse still cannot hang the grid.
-        if (__builtin_amdgcn_ballot_w64(live && i + kIn <= n && (uint32_t)nrec < rcap32) == ~0ull) {
+        if (lanes(live, i <= nin, (uint32_t)nrec < rcap32) == ~0ull) {
             do {
                 window(std::true_type{});
-            } while (__builtin_amdgcn_ballot_w64(i + kIn <= n && (uint32_t)nrec < rcap32) == ~0ull);
+            } while (lanes(i <= nin, (uint32_t)nrec < rcap32) == ~0ull);
             // a match that ran to the stream's end; the group that left the interior has its next
             // window in the general loop below
             if (i + 4 > n) live = false;
@@ -591,9 +627,8 @@ hipError_t launch_lean(const CompressArgs &a, uint64_t *recs, hipStream_t st) {
     const int S = g8 ? 8 : 4;
     const uint32_t stride = split_stride<16, true>(a), tw = split_table_words<true>(a);
     const uint64_t rcap = rec_cap(a);
-    // bit 0: s_setprio 3 on the chain up to the candidate loads; bit 2: the i+1 insert by lane a+1
-    // (EZ_K1S_NEXT1=0 (A/B): by the acceptor, with its own hash)
-    static const int prio = knob("EZ_K1S_PRIO", 1) | (knob("EZ_K1S_NEXT1", 1) ? 4 : 0);
+    // (kLeanPrio's bits; the product build's kernels have them as constants)
+    static const int prio = knob("EZ_K1S_PRIO", kLeanPrio & 1) | (knob("EZ_K1S_NEXT1", 1) ? (kLeanPrio & 4) : 0);
     uint8_t *edge = (uint8_t *)(recs + a.count * rcap);
     // (the edge area's first 128 bytes: the dummy region of idle groups; its last 16: the edge-slot
     // counter)
