@@ -19,6 +19,8 @@
 #include <memory>
 #include <mutex>
 
+#include "ez_k2_layout.h"
+
 namespace ez {
 
 struct CacheEntry {
@@ -170,6 +172,72 @@ class DevCache {
     std::mutex m_;
     std::map<std::pair<int, void *>, std::unique_ptr<CacheEntry>> map_;
     uint64_t tick_ = 0;
+};
+
+// The scratch of a K2 parts route (ez_decompress_parts.hip, ez_decompress_segs_parts.hip), which
+// starts with ez_k2_layout.h's header: the caller's own or a lease of the route's cache, and which
+// lease the last call took, so that its header's counters can be read back afterwards.  One per route,
+// never destroyed (no hipFree after the runtime's teardown).
+struct PartsScratch {
+    DevCache cache;
+    // the last call did not take the route
+    void none() { set(Took{}); }
+    // *w: `bytes` of scratch for a call on st.  The caller's own (own / own_cap) has no counters to report
+    // afterwards; without one, the entry of (the thread's device, st), held by `lease`.
+    // hipErrorOutOfMemory: too small or not to be had, and the caller takes the wave route
+    hipError_t acquire(void *own, uint64_t own_cap, size_t bytes, hipStream_t st, CacheLease &lease, uint8_t **w) {
+        if (own) {
+            if (own_cap < bytes) return hipErrorOutOfMemory;
+            *w = (uint8_t *)own;
+            none();
+            return hipSuccess;
+        }
+        int dev = 0;
+        const hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        lease = cache.acquire(dev, (void *)st);
+        if (!lease->ensure(bytes)) return hipErrorOutOfMemory;
+        *w = (uint8_t *)lease->p;
+        set(Took{true, dev, (void *)st});
+        return hipSuccess;
+    }
+    // the header as the last call left it (zeros where the route did not run, or its scratch was
+    // released since); the caller has synchronised that call's stream
+    hipError_t last(uint32_t h[kHWords]) {
+        memset(h, 0, kHWords * 4);
+        Took t;
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            t = took_;
+        }
+        if (!t.ran) return hipSuccess;
+        int cur = 0;
+        hipError_t e = hipGetDevice(&cur);
+        if (e != hipSuccess) return e;
+        if (cur != t.dev && (e = hipSetDevice(t.dev)) != hipSuccess) return e;
+        {
+            CacheLease lease = cache.acquire(t.dev, t.stream);
+            if (lease->p && lease->cap >= kHWords * 4) {
+                e = hipMemcpy(h, lease->p, kHWords * 4, hipMemcpyDeviceToHost);
+                if (e != hipSuccess) memset(h, 0, kHWords * 4);
+            }
+        }
+        if (cur != t.dev) (void)hipSetDevice(cur);
+        return e;
+    }
+
+  private:
+    struct Took {  // the lease the last call took
+        bool ran = false;
+        int dev = 0;
+        void *stream = nullptr;
+    };
+    void set(const Took &t) {
+        std::lock_guard<std::mutex> g(mu_);
+        took_ = t;
+    }
+    std::mutex mu_;
+    Took took_;
 };
 
 }  // namespace ez

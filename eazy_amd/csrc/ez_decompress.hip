@@ -320,6 +320,15 @@ static hipError_t largest_slot(const DecompressArgs &a, hipStream_t st, uint64_t
     return hipSuccess;
 }
 
+// The exact decoder, a wave per stream and the streams beyond `most` round the grid: every stream of a
+// batch without a slow list and a handle's call (kExactAlone), else the few streams a fast decoder
+// before it listed (kExactBehind)
+constexpr uint64_t kExactAlone = 1u << 30, kExactBehind = 4096;
+static hipError_t launch_exact(const DecompressArgs &a, hipStream_t st, uint64_t most) {
+    hipLaunchKernelGGL(k2_decompress, dim3((unsigned)(a.count < most ? a.count : most)), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
 // K2z: the decoded sizes.  With a workspace the fast kernel first, its hand-overs through the slow list
 // as for the other decoders: to K2g's stage (k2g_size), which sizes the concatenated streams among
 // them and lists the rest again for the exact decoder; without one the exact decoder alone.  Dry, both
@@ -335,18 +344,12 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
     int chunk = a.slow ? size_route(max_len, a.count) : 0;
     // The parts route (ez_decompress_parts.hip) needs the batch's extent to size its records without
     // a read-back: only with the caller's in_bytes hint, and where it measured faster than a wave per
-    // stream (size_parts_chunk) or is forced.  Without its scratch the batch takes the wave route.
-    const int sel = selected_size_route();
-    const int pchunk = a.slow && a.count != 0 && a.in_bytes != 0 && a.count <= (1u << 20) && sel != 'v'
-                           ? size_parts_chunk(max_len, a.count, a.in_bytes, sel == 'p')
-                           : 0;
+    // stream (size_parts_route) or is forced.  Without its scratch the batch takes the wave route.
+    const int pchunk = a.slow ? size_parts_route(max_len, a.count, a.in_bytes) : 0;
     if (a.count == 0 || !a.slow) {
         g_last_size_chunk = chunk;
         size_parts_none();
-        if (a.count == 0) return hipSuccess;
-        const uint64_t grid = a.count < (1u << 30) ? a.count : (1u << 30);
-        hipLaunchKernelGGL(k2_decompress, dim3((unsigned)grid), dim3(64), 0, st, a);
-        return hipGetLastError();
+        return a.count == 0 ? hipSuccess : launch_exact(a, st, kExactAlone);
     }
     // (one memset: the first list's length, and behind its entries K2g's counters and the second list's length)
     uint32_t *second = size_segs_counters(a.slow, a.count) + 2;
@@ -354,7 +357,7 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
     if (e != hipSuccess) return e;
     CacheLease lease;  // (the parts route's scratch, until the wave route behind it is launched)
     if (pchunk) {
-        e = launch_size_parts(a, pchunk, sel != 'p', st, lease, &a.size_gate, &a.size_base);
+        e = launch_size_parts(a, pchunk, selected_size_route() != 'p', st, lease, &a.size_gate, &a.size_base);
         if (e == hipSuccess) chunk = pchunk;
         else if (e != hipErrorOutOfMemory) return e;
         else a.size_gate = nullptr;
@@ -367,25 +370,18 @@ hipError_t launch_decompress_size(const DecompressArgs &a0, uint64_t max_len, hi
     // K2g's walk sizes the concatenated streams of the list; the exact decoder gets the second list
     if ((e = launch_size_segs(a, max_len, st, a0.jws == nullptr)) != hipSuccess) return e;
     a.slow = second;
-    const uint64_t exact_grid = a.count < 4096 ? a.count : 4096;
-    hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
-    return hipGetLastError();
+    return launch_exact(a, st, kExactBehind);
 }
 
 hipError_t launch_exact_dry(const DecompressArgs &a, hipStream_t st) {
-    if (a.count == 0) return hipSuccess;
-    const uint64_t most = a.slow ? 4096 : (1u << 30);
-    hipLaunchKernelGGL(k2_decompress, dim3((unsigned)(a.count < most ? a.count : most)), dim3(64), 0, st, a);
-    return hipGetLastError();
+    return a.count == 0 ? hipSuccess : launch_exact(a, st, a.slow ? kExactBehind : kExactAlone);
 }
 
 hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {
     if (a0.count == 0) return hipSuccess;
     if (a0.handle || !a0.slow) {
         if (!a0.handle) g_last_variant = 'e';
-        uint64_t grid = a0.count < (1u << 30) ? a0.count : (1u << 30);
-        hipLaunchKernelGGL(k2_decompress, dim3((unsigned)grid), dim3(64), 0, st, a0);
-        return hipGetLastError();
+        return launch_exact(a0, st, kExactAlone);
     }
     // EZ_K2=exact (experiments): the exact decoder alone
     static const bool use_exact = knob_str("EZ_K2") && strcmp(knob_str("EZ_K2"), "exact") == 0;
@@ -394,9 +390,7 @@ hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {
         g_last_variant = 'e';
         DecompressArgs b = a0;
         b.slow = nullptr;
-        uint64_t grid = b.count < (1u << 30) ? b.count : (1u << 30);
-        hipLaunchKernelGGL(k2_decompress, dim3((unsigned)grid), dim3(64), 0, st, b);
-        return hipGetLastError();
+        return launch_exact(b, st, kExactAlone);
     }
     DecompressArgs a = a0;
     hipError_t e = largest_slot(a0, st, &a.max_out);
@@ -410,7 +404,6 @@ hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {
         int want = -1;
         (void)g_decompress_variant.compare_exchange_strong(want, sel);
     }
-    const uint64_t exact_grid = a.count < 4096 ? a.count : 4096;
     // Slots under 64 KiB go to K2r's lane per stream; longer ones (C2, C4, the sweep's long streams) to
     // K2t (1 GiB batches, K2 ms, K2r / K2t: 8 KiB 1.89 / 4.99, 16 KiB 1.96 / 4.89, 32 KiB 3.50 / 5.06,
     // 64 KiB 6.69 / 5.31, 128 KiB 13.4 / 5.82, 256 KiB (C2; K2w 12.5) - / 7.0, 1 MiB (K2w 29.7) - / 14.4;
@@ -441,8 +434,7 @@ hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {
         e = launch_decompress_jump(a, st);
         if (e == hipSuccess) {
             g_last_variant = v;
-            hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
-            return hipGetLastError();
+            return launch_exact(a, st, kExactBehind);
         }
         if (e != hipErrorOutOfMemory) return e;
         v = 't';
@@ -460,8 +452,7 @@ hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {
 #if (EZ_EXP & 4096)
         return e;  // debug builds: the hand-over codes stay in the statuses
 #endif
-        hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_exact(a, st, kExactBehind)) != hipSuccess) return e;
         return launch_defer_copy(b, st);
     }
     if (v == 'w') {
@@ -474,15 +465,13 @@ hipError_t launch_decompress(const DecompressArgs &a0, hipStream_t st) {
         if (b.defer && (e = hipMemsetAsync(b.defer, 0, 16, st)) != hipSuccess) return e;
         e = launch_decompress_wave(b, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_exact(a, st, kExactBehind)) != hipSuccess) return e;
         return b.defer ? launch_defer_copy(b, st) : hipSuccess;
     }
     // K2r: one lane per stream with the recent output in an LDS ring
     e = launch_decompress_ring(a, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k2_decompress, dim3((unsigned)exact_grid), dim3(64), 0, st, a);
-    return hipGetLastError();
+    return launch_exact(a, st, kExactBehind);
 }
 
 }  // namespace ez

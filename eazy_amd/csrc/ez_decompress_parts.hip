@@ -2,19 +2,22 @@
 // the few long streams that the wave route (ez_decompress_size.hip) gives one wave each.
 //
 // The steps are ez_k2_parts.h's.  Three kernels on the caller's stream:
-//   kp_init   checks the caller's in_bytes hint against the real extent and lays the streams' parts
-//             out (an exclusive scan of every stream's part count; on the automatic route a stream
-//             that starts with tokens over half of it gets none, kp_probe_wave); on a mismatch it
-//             leaves the gate closed: the next two kernels do nothing.  The wave route, launched
-//             behind them with the gate and the layout as arguments, sizes every stream if the
-//             gate is closed, else the streams without parts;
+//   kp_layout checks the caller's in_bytes hint against the real extent and lays the streams' parts
+//             out (ez_k2_layout.h's steps: an exclusive scan of every stream's part count; on the
+//             automatic route a stream that starts with tokens over half of it gets none,
+//             kp_probe_wave); on a mismatch it leaves the gate closed: the next two kernels do
+//             nothing.  The wave route, launched behind them with the gate and the layout as
+//             arguments, sizes every stream if the gate is closed, else the streams without parts.
+//             K2g's parts route (ez_decompress_segs_parts.hip) lays its parts out with the same
+//             kernel (launch_parts_layout);
 //   kp_first  a wave per part, grid-stride: kz_walk (ez_k2_walk.h) over the part with the warm-up chunk
 //             before it, then sum, reduce, and write the part's record;
 //   kp_order  a wave per stream: follows the true chain through the records, 64 of them per load,
 //             walks again the parts whose record starts elsewhere, and ends as the wave route does:
 //             out_size[s] and EZ_OK, or the stream on the slow list for the exact decoder run dry.
 // The scratch ([header][part bases: count + 1][records]) is sized from the hint alone, so the call
-// never waits for the stream; it is leased from a cache per (device, HIP stream).
+// never waits for the stream; it is the caller's own or leased from a cache per (device, HIP stream)
+// (PartsScratch, ez_cache.h, which also reads the header's counters back after the call).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -28,51 +31,34 @@
 namespace ez {
 namespace {
 
-// the scratch's header words
-enum : int { kHGate = 0, kHParts = 1, kHLaunched = 2, kHJoined = 3, kHWalked = 4, kHWords = 16 };
-constexpr int kInitThreads = 1024;
-
+// The one layout kernel of the parts routes, from ez_k2_layout.h's steps: every stream's part count (none
+// for a stream the probe leaves to the wave route), the gate, and the counts' exclusive scan in base;
+// listed (the size query's stage of K2g's route, may be null): a flag per stream, cleared here
 template <int C>
-__global__ __launch_bounds__(kInitThreads) void kp_init(DecompressArgs A, uint32_t *hdr, uint32_t *base, uint64_t cap, int probe) {
-    __shared__ uint64_t sums[kInitThreads];
+__global__ __launch_bounds__(kLayoutThreads) void kp_layout(const uint8_t *in, const uint64_t *in_off, uint64_t count, uint64_t in_bytes, uint32_t *hdr,
+                                                            uint32_t *base, uint32_t *listed, uint64_t cap, int probe) {
+    __shared__ uint64_t sums[kLayoutThreads];
     const int t = (int)threadIdx.x;
-    const uint64_t per = (A.count + kInitThreads - 1) / kInitThreads;
-    const uint64_t lo = (uint64_t)t * per < A.count ? (uint64_t)t * per : A.count;
-    const uint64_t hi = lo + per < A.count ? lo + per : A.count;
+    const LayoutRange r = layout_range(count, kLayoutThreads, t);
     uint64_t n = 0;
-    for (uint64_t s = lo; s < hi; s++) {
-        const uint64_t nb64 = A.in_off[s + 1] - A.in_off[s];
+    for (uint64_t s = r.lo; s < r.hi; s++) {
+        const uint64_t nb64 = in_off[s + 1] - in_off[s];
         uint32_t parts = kp_parts_of(nb64, C);
         if (probe && parts) {
-            const uint8_t *b = A.in + A.in_off[s];
+            const uint8_t *b = in + in_off[s];
             const uint32_t nb = (uint32_t)nb64;
             if (kp_probe_wave(kz_global_at(b, nb), nb)) parts = 0;
         }
         base[s] = parts;
+        if (listed) listed[s] = 0;
         n += parts;
     }
     sums[t] = n;
     __syncthreads();
-    if (t == 0) {
-        uint64_t run = 0;
-        for (int k = 0; k < kInitThreads; k++) {
-            const uint64_t v = sums[k];
-            sums[k] = run;
-            run += v;
-        }
-        // the records are sized from the hint: nothing indexes them unless the real extent is within it
-        const bool ok = A.in_off[A.count] >= A.in_off[0] && A.in_off[A.count] - A.in_off[0] <= A.in_bytes && run <= cap;
-        hdr[kHParts] = ok ? (uint32_t)run : 0u;
-        hdr[kHGate] = ok ? 1u : 0u;
-        base[A.count] = ok ? (uint32_t)run : 0u;
-    }
+    // the records are sized from the hint: nothing indexes them unless the real extent is within it
+    if (t == 0) (void)layout_gate(sums, kLayoutThreads, in_off, count, in_bytes, cap, hdr, base);
     __syncthreads();
-    uint64_t run = sums[t];
-    for (uint64_t s = lo; s < hi; s++) {  // the part counts become their exclusive scan, in place
-        const uint32_t parts = base[s];
-        base[s] = (uint32_t)run;  // (wraps only where the gate stays closed)
-        run += parts;
-    }
+    layout_scan(base, r, sums[t]);
 }
 
 // One part of the stream b[0 .. nb) at ps, by the whole wave: its record for the chain that enters at
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(64) void kp_first(DecompressArgs A, uint32_t *hdr, 
         if (lane_id() == 0) recs[g] = r;
         done++;
     }
-    if (lane_id() == 0 && done) atomicAdd(&hdr[kHLaunched], done);
+    if (lane_id() == 0 && done) atomicAdd(&hdr[kHFirst], done);
 }
 
 template <int C>
@@ -178,76 +164,65 @@ __global__ __launch_bounds__(64) void kp_order(DecompressArgs A, uint32_t *hdr, 
     }
     if (lane == 0) {
         if (joined) atomicAdd(&hdr[kHJoined], joined);
-        if (walked) atomicAdd(&hdr[kHWalked], walked);
+        if (walked) atomicAdd(&hdr[kHAgain], walked);
     }
 }
+
+// the scratch: [header][part bases: count + 1][records: cap]
+size_t recs_at(uint64_t count) { return (((size_t)kHWords + count + 1) * 4 + 15) / 16 * 16; }
 
 template <int C>
 hipError_t launch_parts(const DecompressArgs &a, uint8_t *w, uint64_t cap, int probe, hipStream_t st) {
     uint32_t *hdr = (uint32_t *)w;
     uint32_t *base = hdr + kHWords;
-    KpRec *recs = (KpRec *)(w + (((size_t)kHWords + a.count + 1) * 4 + 15) / 16 * 16);
-    hipError_t e = hipMemsetAsync(hdr, 0, kHWords * 4, st);
+    KpRec *recs = (KpRec *)(w + recs_at(a.count));
+    const hipError_t e = launch_parts_layout(C, a.in, a.in_off, a.count, a.in_bytes, hdr, base, nullptr, cap, probe, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kp_init<C>, dim3(1), dim3(kInitThreads), 0, st, a, hdr, base, cap, probe);
     // the chip's LDS holds two such blocks per CU; the parts beyond go round the grid
     hipLaunchKernelGGL(kp_first<C>, dim3((unsigned)(cap < 2048 ? cap : 2048)), dim3(64), 0, st, a, hdr, base, recs);
     hipLaunchKernelGGL(kp_order<C>, dim3((unsigned)(a.count < 2048 ? a.count : 2048)), dim3(64), 0, st, a, hdr, base, recs);
     return hipGetLastError();
 }
 
-struct PartsLast {
-    std::mutex mu;
-    bool ran = false;
-    int dev = 0;
-    void *stream = nullptr;
-} g_last;
+PartsScratch &scratch() {
+    static PartsScratch *x = new PartsScratch();
+    return *x;
+}
 
 }  // namespace
 
-DevCache &size_cache() {
-    static DevCache *c = new DevCache();  // (never destroyed: no hipFree after the runtime's teardown)
-    return *c;
+hipError_t launch_parts_layout(int chunk, const uint8_t *in, const uint64_t *in_off, uint64_t count, uint64_t in_bytes, uint32_t *hdr, uint32_t *base,
+                               uint32_t *listed, uint64_t cap, int probe, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(hdr, 0, kHWords * 4, st);
+    if (e != hipSuccess) return e;
+    if (chunk == 1024) hipLaunchKernelGGL(kp_layout<1024>, dim3(1), dim3(kLayoutThreads), 0, st, in, in_off, count, in_bytes, hdr, base, listed, cap, probe);
+    else hipLaunchKernelGGL(kp_layout<256>, dim3(1), dim3(kLayoutThreads), 0, st, in, in_off, count, in_bytes, hdr, base, listed, cap, probe);
+    return hipGetLastError();
 }
+
+DevCache &size_cache() { return scratch().cache; }
 
 static std::atomic<int> g_size_route{0};  // 0: automatic; 'p', 'v'
 void select_size_route(int v) { g_size_route = v; }
 int selected_size_route() { return g_size_route; }
 
-void size_parts_none() {
-    std::lock_guard<std::mutex> g(g_last.mu);
-    g_last.ran = false;
-}
+void size_parts_none() { scratch().none(); }
 
-// bytes of scratch the route needs for a batch (either chunk size): a synchronous caller that owns
-// its scratch (a Reader handle) sizes it with this and passes it as DecompressArgs.jws / jws_cap
+// bytes of scratch the route needs for a batch (either chunk size; 0: more parts than the route takes):
+// a synchronous caller that owns its scratch (a Reader handle) sizes it with this and passes it as
+// DecompressArgs.jws / jws_cap
 uint64_t size_parts_workspace_bytes(uint64_t count, uint64_t in_bytes) {
-    const uint64_t cap = in_bytes / kp_part_bytes(256) + count + 1;
-    return (((uint64_t)kHWords + count + 1) * 4 + 15) / 16 * 16 + cap * sizeof(KpRec);
+    const uint64_t cap = parts_cap(in_bytes, kp_part_bytes(256), count);
+    return cap ? recs_at(count) + cap * sizeof(KpRec) : 0;
 }
 
 hipError_t launch_size_parts(const DecompressArgs &a, int chunk, bool probe, hipStream_t st, CacheLease &lease, const uint32_t **gate,
                              const uint32_t **base) {
-    const uint32_t P = kp_part_bytes((uint32_t)chunk);
-    const uint64_t cap = a.in_bytes / P + a.count + 1;  // every stream's parts: at most its bytes / P, rounded up
-    if (cap >= (1ull << 31)) return hipErrorOutOfMemory;
-    const size_t bytes = (((size_t)kHWords + a.count + 1) * 4 + 15) / 16 * 16 + (size_t)cap * sizeof(KpRec);
-    uint8_t *w = (uint8_t *)a.jws;
-    if (w) {  // the caller's own scratch: no counters to report afterwards
-        if (a.jws_cap < bytes) return hipErrorOutOfMemory;
-        size_parts_none();
-    } else {
-        int dev = 0;
-        const hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        lease = size_cache().acquire(dev, (void *)st);
-        if (!lease->ensure(bytes)) return hipErrorOutOfMemory;  // (the caller takes the wave route)
-        w = (uint8_t *)lease->p;
-        std::lock_guard<std::mutex> g(g_last.mu);
-        g_last.ran = true;
-        g_last.dev = dev;
-        g_last.stream = (void *)st;
-    }
+    const uint64_t cap = parts_cap(a.in_bytes, kp_part_bytes((uint32_t)chunk), a.count);
+    if (cap == 0) return hipErrorOutOfMemory;
+    uint8_t *w = nullptr;
+    const hipError_t e = scratch().acquire(a.jws, a.jws_cap, recs_at(a.count) + (size_t)cap * sizeof(KpRec), st, lease, &w);
+    if (e != hipSuccess) return e;
     *gate = (const uint32_t *)w + kHGate;
     *base = (const uint32_t *)w + kHWords;
     return chunk == 1024 ? launch_parts<1024>(a, w, cap, probe, st) : launch_parts<256>(a, w, cap, probe, st);
@@ -256,34 +231,11 @@ hipError_t launch_size_parts(const DecompressArgs &a, int chunk, bool probe, hip
 // of the last query: parts launched, parts whose record the true chain took, parts walked again
 // (zeros where the parts route did not run); the caller has synchronised the query's stream
 hipError_t size_parts_last(uint64_t counts[3]) {
-    counts[0] = counts[1] = counts[2] = 0;
-    bool ran;
-    int dev;
-    void *stream;
-    {
-        std::lock_guard<std::mutex> g(g_last.mu);
-        ran = g_last.ran;
-        dev = g_last.dev;
-        stream = g_last.stream;
-    }
-    if (!ran) return hipSuccess;
-    int cur = 0;
-    hipError_t e = hipGetDevice(&cur);
-    if (e != hipSuccess) return e;
-    if (cur != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
-    {
-        CacheLease lease = size_cache().acquire(dev, stream);
-        if (lease->p && lease->cap >= kHWords * 4) {  // (else released since: nothing to report)
-            uint32_t h[kHWords];
-            e = hipMemcpy(h, lease->p, sizeof h, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) {
-                counts[0] = h[kHLaunched];
-                counts[1] = h[kHJoined];
-                counts[2] = h[kHWalked];
-            }
-        }
-    }
-    if (cur != dev) (void)hipSetDevice(cur);
+    uint32_t h[kHWords];
+    const hipError_t e = scratch().last(h);
+    counts[0] = h[kHFirst];
+    counts[1] = h[kHJoined];
+    counts[2] = h[kHAgain];
     return e;
 }
 

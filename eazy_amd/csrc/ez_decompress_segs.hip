@@ -279,11 +279,10 @@ hipError_t launch_segments(const SegsArgs &a0, uint64_t max_len, void *workspace
     const unsigned grid = (unsigned)(a.count < 8192 ? a.count : 8192);
     hipError_t e;
     // The parts route (ez_decompress_segs_parts.hip) needs the batch's extent to size its records
-    // without a read-back: only with the caller's in_bytes hint, and where segs_parts_chunk picks it or
+    // without a read-back: only with the caller's in_bytes hint, and where segs_parts_route picks it or
     // it is forced.  Without its scratch the batch takes the wave route.
     a.parts_gate = a.parts_base = nullptr;
-    const int sel = selected_segments_route();
-    int pchunk = a.count != 0 && a.in_bytes != 0 && a.count <= (1u << 20) && sel != 'v' ? segs_parts_chunk(max_len, a.count, a.in_bytes, sel == 'p') : 0;
+    int pchunk = segs_parts_route(max_len, a.count, a.in_bytes);
     CacheLease please;  // (its scratch, until the last launch)
     if (pchunk) {
         e = launch_segs_parts(a, pchunk, st, please);
@@ -327,8 +326,7 @@ hipError_t launch_size_segs(const DecompressArgs &a, uint64_t max_len, hipStream
     // Reader handle).  Without its scratch k2g_size walks the whole list.
     const uint32_t *gate = nullptr, *base = nullptr;
     CacheLease please;
-    const int sel = selected_segments_route();
-    const int pchunk = parts && a.in_bytes != 0 && a.count <= (1u << 20) && sel != 'v' ? segs_parts_chunk(max_len, a.count, a.in_bytes, sel == 'p') : 0;
+    const int pchunk = parts ? segs_parts_route(max_len, a.count, a.in_bytes) : 0;
     if (pchunk) {
         const hipError_t e = launch_size_segs_parts(a, pchunk, st, please, &gate, &base);
         if (e == hipErrorOutOfMemory) gate = base = nullptr;
@@ -408,10 +406,7 @@ hipError_t launch_decompress_segmented(const DecompressArgs &a, hipStream_t st) 
         // room for a segment per stream and some more, or for what the scratch held last time
         uint64_t cap = a.count + a.count / 2 + 1024;
         // the query's parts route, where the caller's in_bytes hint lets it run
-        const uint64_t pbytes = a.in_bytes != 0 && a.count <= (1u << 20) && selected_segments_route() != 'v' &&
-                                        segs_parts_chunk(0, a.count, a.in_bytes, selected_segments_route() == 'p')
-                                    ? segs_parts_workspace_bytes(a.count, a.in_bytes)
-                                    : 0;
+        const uint64_t pbytes = segs_parts_route(0, a.count, a.in_bytes) ? segs_parts_workspace_bytes(a.count, a.in_bytes) : 0;
         for (uint64_t step = 1ull << 36; step; step >>= 1)
             if (seg_scratch(nullptr, a.count, cap + step, pbytes).bytes <= lease->cap) cap += step;
         uint64_t h[5] = {0, 0, 0, 0, 0};

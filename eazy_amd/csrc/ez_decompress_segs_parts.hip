@@ -4,9 +4,10 @@
 //
 // The steps are ez_k2_segs_parts.h's, over K2z's part grid (ez_k2_parts.h).  Kernels on the caller's
 // stream, which never wait for it:
-//   ks_init   checks the caller's in_bytes hint against the real extent and lays the streams' parts
+//   kp_layout (ez_decompress_parts.hip's, through launch_parts_layout; the steps are ez_k2_layout.h's)
+//             checks the caller's in_bytes hint against the real extent and lays the streams' parts
 //             out (an exclusive scan of every stream's part count); on a mismatch it leaves the gate
-//             closed: the other kernels of this file do nothing, and k2g_walk, launched behind them
+//             closed: the kernels of this file do nothing, and k2g_walk, launched behind them
 //             with the gate and the layout in its arguments, walks every stream, else only the
 //             streams without parts (empty, 2 GiB or more);
 //   ks_first  a wave per part, grid-stride: kz_walk (ez_k2_walk.h) over the part with the warm-up chunk
@@ -19,16 +20,16 @@
 //   ks_fill   a wave per part whose record holds a Reset and whose entry state is live: ks_block
 //             from the entry state, which writes the part's cuts in place.  Nothing is walked twice by
 //             one wave for a stream of many cuts: the fill is parallel.
-// The size query's stage (launch_size_segs) runs ks_init, ks_mark (a flag per stream of the fast
-// kernels' list), ks_first and ks_order over the listed streams that have parts: the order pass then
-// ends as k2g_size does, and there is no fill.
+// The size query's stage (launch_size_segs) runs kp_layout (which clears a flag per stream), ks_mark (sets
+// the flag of every stream of the fast kernels' list), ks_first and ks_order over the listed streams
+// that have parts: the order pass then ends as k2g_size does, and there is no fill.
 // The scratch ([header][part bases: count + 1][listed: count][records][entry states]) is sized from the hint alone.
-// A direct query leases it per (device, HIP stream) from a cache; the segmented decode carves it out of
-// its own lease and passes it down (SegsArgs.pws).  Nothing in it is carried from call to call.
+// A direct query leases it per (device, HIP stream) from a cache (PartsScratch, ez_cache.h, which also reads
+// the header's counters back); the segmented decode carves it out of its own lease and passes it down
+// (SegsArgs.pws).  Nothing in it is carried from call to call.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <mutex>
 
 #include "ez_bytes.h"
 #include "ez_cache.h"
@@ -38,10 +39,6 @@
 
 namespace ez {
 namespace {
-
-// the scratch's header words
-enum : int { kHGate = 0, kHParts = 1, kHFirst = 2, kHJoined = 3, kHAgain = 4, kHFilled = 5, kHWords = 16 };
-constexpr int kInitThreads = 1024;
 
 struct Scratch {
     uint32_t *hdr, *base, *listed;
@@ -61,44 +58,6 @@ Scratch scratch_at(uint8_t *w, uint64_t count, uint64_t cap) {
     o += (size_t)cap * sizeof(KsEnt);
     x.bytes = o;
     return x;
-}
-
-template <int C>
-__global__ __launch_bounds__(kInitThreads) void ks_init(SegsArgs A, uint32_t *hdr, uint32_t *base, uint32_t *listed, uint64_t cap) {
-    __shared__ uint64_t sums[kInitThreads];
-    const int t = (int)threadIdx.x;
-    const uint64_t per = (A.count + kInitThreads - 1) / kInitThreads;
-    const uint64_t lo = (uint64_t)t * per < A.count ? (uint64_t)t * per : A.count;
-    const uint64_t hi = lo + per < A.count ? lo + per : A.count;
-    uint64_t n = 0;
-    for (uint64_t s = lo; s < hi; s++) {
-        const uint32_t parts = kp_parts_of(A.in_off[s + 1] - A.in_off[s], C);
-        base[s] = parts;
-        if (listed) listed[s] = 0;
-        n += parts;
-    }
-    sums[t] = n;
-    __syncthreads();
-    if (t == 0) {
-        uint64_t run = 0;
-        for (int k = 0; k < kInitThreads; k++) {
-            const uint64_t v = sums[k];
-            sums[k] = run;
-            run += v;
-        }
-        // the records are sized from the hint: nothing indexes them unless the real extent is within it
-        const bool ok = A.in_off[A.count] >= A.in_off[0] && A.in_off[A.count] - A.in_off[0] <= A.in_bytes && run <= cap;
-        hdr[kHParts] = ok ? (uint32_t)run : 0u;
-        hdr[kHGate] = ok ? 1u : 0u;
-        base[A.count] = ok ? (uint32_t)run : 0u;
-    }
-    __syncthreads();
-    uint64_t run = sums[t];
-    for (uint64_t s = lo; s < hi; s++) {  // the part counts become their exclusive scan, in place
-        const uint32_t parts = base[s];
-        base[s] = (uint32_t)run;  // (wraps only where the gate stays closed)
-        run += parts;
-    }
 }
 
 __device__ __forceinline__ KsSum sum_down(const KsSum &r, int d) {
@@ -323,31 +282,25 @@ __global__ __launch_bounds__(64) void ks_fill(SegsArgs A, uint32_t *hdr, const u
     if (lane == 0 && filled) atomicAdd(&hdr[kHFilled], filled);
 }
 
-struct PartsLast {
-    std::mutex mu;
-    bool ran = false;
-    int dev = 0;
-    void *stream = nullptr;
-} g_last;
+PartsScratch &scratch() {
+    static PartsScratch *x = new PartsScratch();
+    return *x;
+}
 
 std::atomic<int> g_route{0};  // 0: automatic; 'p', 'v'
 
 }  // namespace
 
-DevCache &segs_parts_cache() {
-    static DevCache *c = new DevCache();  // (never destroyed: no hipFree after the runtime's teardown)
-    return *c;
-}
+DevCache &segs_parts_cache() { return scratch().cache; }
 
 void select_segments_route(int v) { g_route = v; }
 int selected_segments_route() { return g_route; }
 
-void segs_parts_none() {
-    std::lock_guard<std::mutex> g(g_last.mu);
-    g_last.ran = false;
-}
+void segs_parts_none() { scratch().none(); }
 
-// The parts route's chunk for a segment query whose caller gave its input bytes, 0: the wave route.
+// The parts route's chunk for a segment query, 0: the wave route, which takes every batch whose caller
+// did not give its input bytes, an empty one, one of more than 2^20 streams, and all of them under
+// ez_select_segments_route('v').
 // Forced (ez_select_segments_route('p')): at any length, 1,024 where the wave route takes 1,024, else
 // 256.  Automatic, only where it measured faster than a wave per stream (tools/segments_bench.py --route
 // --forced, profiles/r08_segments_parts.txt; 64 KiB frames of log data, the query alone,
@@ -363,38 +316,45 @@ void segs_parts_none() {
 // measured at that count.
 // Without a max_len hint (the segmented decode's query) the batch's mean length stands in, which is
 // at most the longest.
-int segs_parts_chunk(uint64_t max_len, uint64_t count, uint64_t in_bytes, bool forced) {
-    if (forced) return size_chunk(max_len) == 1024 ? 1024 : 256;
-    if (max_len == 0) max_len = in_bytes / (count ? count : 1);
+int segs_parts_route(uint64_t max_len, uint64_t count, uint64_t in_bytes) {
+    const int sel = selected_segments_route();
+    if (count == 0 || in_bytes == 0 || count > (1u << 20) || sel == 'v') return 0;
+    if (sel == 'p') return size_chunk(max_len) == 1024 ? 1024 : 256;
+    if (max_len == 0) max_len = in_bytes / count;
     return count <= 64 && max_len >= (480u << 10) ? 1024 : 0;
 }
 
-// bytes of scratch the route needs for a batch (either chunk size)
+// bytes of scratch the route needs for a batch (either chunk size; 0: more parts than the route takes)
 uint64_t segs_parts_workspace_bytes(uint64_t count, uint64_t in_bytes) {
-    return scratch_at(nullptr, count, in_bytes / kp_part_bytes(256) + count + 1).bytes;
+    const uint64_t cap = parts_cap(in_bytes, kp_part_bytes(256), count);
+    return cap ? scratch_at(nullptr, count, cap).bytes : 0;
 }
 
-template <int C>
-static hipError_t launch_front(const SegsArgs &a, const Scratch &x, uint64_t cap, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(x.hdr, 0, kHWords * 4, st);
+// The passes in front of the wave route's kernels: the layout, a wave per part, a wave per stream.  SIZE:
+// the size query's stage, over the streams of the fast kernels' list only (ks_mark)
+template <int C, bool SIZE>
+static hipError_t launch_front(const SegsArgs &a, const Scratch &x, uint64_t cap, const KsSize &z, hipStream_t st) {
+    uint32_t *listed = SIZE ? x.listed : nullptr;
+    const hipError_t e = launch_parts_layout(C, a.in, a.in_off, a.count, a.in_bytes, x.hdr, x.base, listed, cap, 0, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ks_init<C>, dim3(1), dim3(kInitThreads), 0, st, a, x.hdr, x.base, (uint32_t *)nullptr, cap);
+    if (SIZE) hipLaunchKernelGGL(ks_mark, dim3((unsigned)((a.count + 255) / 256 < 1024 ? (a.count + 255) / 256 : 1024)), dim3(256), 0, st, z, a.count, x.hdr, listed);
     // the chip's LDS holds two such blocks per CU at chunk 1,024; the parts beyond go round the grid
-    hipLaunchKernelGGL(ks_first<C>, dim3((unsigned)(cap < 2048 ? cap : 2048)), dim3(64), 0, st, a, x.hdr, x.base, (const uint32_t *)nullptr, x.recs);
-    hipLaunchKernelGGL((ks_order<C, false>), dim3((unsigned)(a.count < 2048 ? a.count : 2048)), dim3(64), 0, st, a, x.hdr, x.base, x.recs, x.ents,
-                       (const uint32_t *)nullptr, KsSize{});
+    hipLaunchKernelGGL(ks_first<C>, dim3((unsigned)(cap < 2048 ? cap : 2048)), dim3(64), 0, st, a, x.hdr, x.base, (const uint32_t *)listed, x.recs);
+    hipLaunchKernelGGL((ks_order<C, SIZE>), dim3((unsigned)(a.count < 2048 ? a.count : 2048)), dim3(64), 0, st, a, x.hdr, x.base, x.recs, x.ents,
+                       (const uint32_t *)listed, z);
     return hipGetLastError();
 }
 
-template <int C>
-static hipError_t launch_size_front(const SegsArgs &a, const Scratch &x, uint64_t cap, const KsSize &z, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(x.hdr, 0, kHWords * 4, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ks_init<C>, dim3(1), dim3(kInitThreads), 0, st, a, x.hdr, x.base, x.listed, cap);
-    hipLaunchKernelGGL(ks_mark, dim3((unsigned)((a.count + 255) / 256 < 1024 ? (a.count + 255) / 256 : 1024)), dim3(256), 0, st, z, a.count, x.hdr, x.listed);
-    hipLaunchKernelGGL(ks_first<C>, dim3((unsigned)(cap < 2048 ? cap : 2048)), dim3(64), 0, st, a, x.hdr, x.base, x.listed, x.recs);
-    hipLaunchKernelGGL((ks_order<C, true>), dim3((unsigned)(a.count < 2048 ? a.count : 2048)), dim3(64), 0, st, a, x.hdr, x.base, x.recs, x.ents, x.listed, z);
-    return hipGetLastError();
+// a batch's scratch at a chunk size, the caller's own or leased, and the records it holds
+// (hipErrorOutOfMemory: not to be had, nothing is launched)
+static hipError_t scratch_for(uint64_t in_bytes, int chunk, uint64_t count, void *own, uint64_t own_cap, hipStream_t st, CacheLease &lease, Scratch &x,
+                              uint64_t &cap) {
+    cap = parts_cap(in_bytes, kp_part_bytes((uint32_t)chunk), count);
+    if (cap == 0) return hipErrorOutOfMemory;
+    uint8_t *w = nullptr;
+    const hipError_t e = scratch().acquire(own, own_cap, scratch_at(nullptr, count, cap).bytes, st, lease, &w);
+    if (e == hipSuccess) x = scratch_at(w, count, cap);
+    return e;
 }
 
 // The size query's stage for the handed-over streams that have parts: the first and order passes in
@@ -402,21 +362,11 @@ static hipError_t launch_size_front(const SegsArgs &a, const Scratch &x, uint64_
 // k2g_size behind it, which then walks only the listed streams without parts (all of them where the
 // gate stays closed).  lease: the scratch, held until k2g_size is launched.
 hipError_t launch_size_segs_parts(const DecompressArgs &a, int chunk, hipStream_t st, CacheLease &lease, const uint32_t **gate, const uint32_t **base) {
-    const uint32_t P = kp_part_bytes((uint32_t)chunk);
-    const uint64_t cap = a.in_bytes / P + a.count + 1;
-    if (cap >= (1ull << 31)) return hipErrorOutOfMemory;
-    int dev = 0;
-    const hipError_t e = hipGetDevice(&dev);
+    Scratch x;
+    uint64_t cap;
+    // (the header's counters are this stage's now: segs_parts_last reports them, with no parts filled)
+    const hipError_t e = scratch_for(a.in_bytes, chunk, a.count, nullptr, 0, st, lease, x, cap);
     if (e != hipSuccess) return e;
-    lease = segs_parts_cache().acquire(dev, (void *)st);
-    if (!lease->ensure(scratch_at(nullptr, a.count, cap).bytes)) return hipErrorOutOfMemory;
-    {  // (the header's counters are this stage's now: segs_parts_last reports them, with no parts filled)
-        std::lock_guard<std::mutex> g(g_last.mu);
-        g_last.ran = true;
-        g_last.dev = dev;
-        g_last.stream = (void *)st;
-    }
-    const Scratch x = scratch_at((uint8_t *)lease->p, a.count, cap);
     SegsArgs q{};
     q.in = a.in;
     q.in_off = a.in_off;
@@ -426,36 +376,19 @@ hipError_t launch_size_segs_parts(const DecompressArgs &a, int chunk, hipStream_
     const KsSize z{a.slow, a.out_size, a.status, size_segs_counters(a.slow, a.count)};
     *gate = x.hdr + kHGate;
     *base = x.base;
-    return chunk == 1024 ? launch_size_front<1024>(q, x, cap, z, st) : launch_size_front<256>(q, x, cap, z, st);
+    return chunk == 1024 ? launch_front<1024, true>(q, x, cap, z, st) : launch_front<256, true>(q, x, cap, z, st);
 }
 
 hipError_t launch_segs_parts(SegsArgs &a, int chunk, hipStream_t st, CacheLease &lease) {
-    const uint32_t P = kp_part_bytes((uint32_t)chunk);
-    const uint64_t cap = a.in_bytes / P + a.count + 1;  // every stream's parts: at most its bytes / P, rounded up
-    if (cap >= (1ull << 31)) return hipErrorOutOfMemory;
-    const size_t bytes = scratch_at(nullptr, a.count, cap).bytes;
-    uint8_t *w = (uint8_t *)a.pws;
-    if (w) {  // the caller's own scratch: no counters to report afterwards
-        if (a.pws_cap < bytes) return hipErrorOutOfMemory;
-        segs_parts_none();
-    } else {
-        int dev = 0;
-        const hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        lease = segs_parts_cache().acquire(dev, (void *)st);
-        if (!lease->ensure(bytes)) return hipErrorOutOfMemory;  // (the caller takes the wave route)
-        w = (uint8_t *)lease->p;
-        std::lock_guard<std::mutex> g(g_last.mu);
-        g_last.ran = true;
-        g_last.dev = dev;
-        g_last.stream = (void *)st;
-    }
-    const Scratch x = scratch_at(w, a.count, cap);
+    Scratch x;
+    uint64_t cap;
+    const hipError_t e = scratch_for(a.in_bytes, chunk, a.count, a.pws, a.pws_cap, st, lease, x, cap);
+    if (e != hipSuccess) return e;
     a.parts_gate = x.hdr + kHGate;
     a.parts_base = x.base;
-    a.pws = w;
+    a.pws = x.hdr;
     a.pws_cap = cap;  // (from here on: the records the scratch holds)
-    return chunk == 1024 ? launch_front<1024>(a, x, cap, st) : launch_front<256>(a, x, cap, st);
+    return chunk == 1024 ? launch_front<1024, false>(a, x, cap, KsSize{}, st) : launch_front<256, false>(a, x, cap, KsSize{}, st);
 }
 
 hipError_t launch_segs_parts_fill(const SegsArgs &a, int chunk, hipStream_t st) {
@@ -471,35 +404,12 @@ hipError_t launch_segs_parts_fill(const SegsArgs &a, int chunk, hipStream_t st) 
 // pass, records taken as they stood, parts walked again, parts filled (zeros where the route did not
 // run); the caller has synchronised the query's stream
 hipError_t segs_parts_last(uint64_t counts[4]) {
-    counts[0] = counts[1] = counts[2] = counts[3] = 0;
-    bool ran;
-    int dev;
-    void *stream;
-    {
-        std::lock_guard<std::mutex> g(g_last.mu);
-        ran = g_last.ran;
-        dev = g_last.dev;
-        stream = g_last.stream;
-    }
-    if (!ran) return hipSuccess;
-    int cur = 0;
-    hipError_t e = hipGetDevice(&cur);
-    if (e != hipSuccess) return e;
-    if (cur != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
-    {
-        CacheLease lease = segs_parts_cache().acquire(dev, stream);
-        if (lease->p && lease->cap >= kHWords * 4) {  // (else released since: nothing to report)
-            uint32_t h[kHWords];
-            e = hipMemcpy(h, lease->p, sizeof h, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) {
-                counts[0] = h[kHFirst];
-                counts[1] = h[kHJoined];
-                counts[2] = h[kHAgain];
-                counts[3] = h[kHFilled];
-            }
-        }
-    }
-    if (cur != dev) (void)hipSetDevice(cur);
+    uint32_t h[kHWords];
+    const hipError_t e = scratch().last(h);
+    counts[0] = h[kHFirst];
+    counts[1] = h[kHJoined];
+    counts[2] = h[kHAgain];
+    counts[3] = h[kHFilled];
     return e;
 }
 

@@ -117,8 +117,10 @@ int size_route(uint64_t max_len, uint64_t count) {
     return max_len != 0 && max_len <= 4096 && count >= kZLaneStreams ? 1 : size_chunk(max_len);
 }
 
-// The parts route's chunk for a batch whose caller gave its input bytes, 0: the wave route.  Forced
-// (ez_select_size_route('p')): at any length, 1,024 where the wave route takes 1,024, else 256.
+// The parts route's chunk for a batch, 0: the wave route, which takes every batch whose caller did not
+// give its input bytes, an empty one, one of more than 2^20 streams, and all of them under
+// ez_select_size_route('v').  Forced (ez_select_size_route('p')): at any length, 1,024 where the wave
+// route takes 1,024, else 256.
 // Automatic, only where it measured faster than a wave per stream (tools/size_parts_bench.py, DESIGN
 // §4 K2z; ms, wave / parts 256 / parts 1,024):
 //   one stream from 240 KiB of input on, chunk 1,024 (one log stream of 0.25 MB compressed 1.76 / 0.70 /
@@ -128,9 +130,10 @@ int size_route(uint64_t max_len, uint64_t count) {
 //     literals are the wave route's by the probe: 0.073 on the wave route alone, 0.052 automatic).
 // More streams keep a wave each, which fills the chip (1,024 x 1 MiB logs 4.06 / 4.48 / 6.64, C2 2.25 /
 // 3.58 / 6.25).
-int size_parts_chunk(uint64_t max_len, uint64_t count, uint64_t in_bytes, bool forced) {
-    if (forced) return size_chunk(max_len) == 1024 ? 1024 : 256;
-    (void)in_bytes;
+int size_parts_route(uint64_t max_len, uint64_t count, uint64_t in_bytes) {
+    const int sel = selected_size_route();
+    if (count == 0 || in_bytes == 0 || count > (1u << 20) || sel == 'v') return 0;
+    if (sel == 'p') return size_chunk(max_len) == 1024 ? 1024 : 256;
     if (count == 1) return max_len >= (240u << 10) ? 1024 : 0;
     return count <= 64 && max_len > (512u << 10) ? 256 : 0;
 }

@@ -256,7 +256,12 @@ hipError_t launch_size_fast(const DecompressArgs &a, int route, hipStream_t s);
 // 1,024; needs a.in_bytes.  probe: streams that start with tokens over half of them get no parts.
 // *gate, *base: DecompressArgs.size_gate and size_base for the wave route launched behind it; lease: the scratch, held until that launch.  (hipErrorOutOfMemory: the scratch
 // could not be had, nothing was launched)
-int size_parts_chunk(uint64_t max_len, uint64_t count, uint64_t in_bytes, bool forced);  // its chunk; 0: the wave route
+int size_parts_route(uint64_t max_len, uint64_t count, uint64_t in_bytes);  // its chunk for a batch; 0: the wave route
+// The part layout of this route and of K2g's (kp_layout, the steps of ez_k2_layout.h), chunk 256 or 1,024:
+// zeroes the scratch's header hdr, then the gate, the batch's parts and base[0 .. count]; listed (may be
+// null): count flags, cleared; cap: the records the scratch holds (parts_cap); probe: K2z's
+hipError_t launch_parts_layout(int chunk, const uint8_t *in, const uint64_t *in_off, uint64_t count, uint64_t in_bytes, uint32_t *hdr, uint32_t *base,
+                               uint32_t *listed, uint64_t cap, int probe, hipStream_t s);
 class CacheLease;
 hipError_t launch_size_parts(const DecompressArgs &a, int chunk, bool probe, hipStream_t s, CacheLease &lease, const uint32_t **gate,
                              const uint32_t **base);
@@ -299,11 +304,11 @@ uint64_t segments_workspace_bytes(uint64_t count);
 // max_len: the caller's hint, the longest input stream (0 = unknown), which picks the chunk (size_chunk)
 hipError_t launch_segments(const SegsArgs &a, uint64_t max_len, void *workspace, hipStream_t s);
 // K2g's parts route: every stream's chain cut over many waves, chunk 256 or 1,024; needs a.in_bytes.
-// launch_segs_parts: init, first and order passes (seg_idx[s] for the streams with parts, the parts'
+// launch_segs_parts: layout, first and order passes (seg_idx[s] for the streams with parts, the parts'
 // entry states); sets a's parts_gate / parts_base, and pws / pws_cap for launch_segs_parts_fill, which
 // goes behind k2g_scan and k2g_heads.  lease: the scratch, held until the last launch.
 // (hipErrorOutOfMemory: the scratch could not be had, nothing was launched)
-int segs_parts_chunk(uint64_t max_len, uint64_t count, uint64_t in_bytes, bool forced);  // its chunk; 0: the wave route
+int segs_parts_route(uint64_t max_len, uint64_t count, uint64_t in_bytes);  // its chunk for a batch; 0: the wave route
 hipError_t launch_segs_parts(SegsArgs &a, int chunk, hipStream_t s, CacheLease &lease);
 hipError_t launch_segs_parts_fill(const SegsArgs &a, int chunk, hipStream_t s);
 uint64_t segs_parts_workspace_bytes(uint64_t count, uint64_t in_bytes);

@@ -279,6 +279,50 @@ def test_batches(cuda, count):
     assert got[256][1] > 0
 
 
+_MANY = {}
+
+
+def many_streams(count):
+    """(streams, oracle results) of a batch past kp_layout's 1,024 threads, where a thread lays out
+    several streams and the last threads none: tiny valid streams of one part (the header and a short
+    literal), every 97th a long one of two parts at chunk 256, every 101st empty.  Built and sized by
+    the oracle once; a smaller count is a prefix."""
+    if not _MANY:
+        ins = []
+        for s in range(2049):
+            if s % 101 == 100:
+                ins.append(b"")
+            elif s % 97 == 96:
+                ins.append(_long(17000 + s, 389))
+            else:
+                ins.append(HDR + lit(bytes([97 + s % 26]) * (1 + s % 5)))
+        _MANY["ins"], _MANY["want"] = ins, _want(ins)
+    return _MANY["ins"][:count], _MANY["want"][:count]
+
+
+@pytest.mark.parametrize("count", [1025, 2049])
+def test_layout_of_several_streams_per_thread(cuda, count):
+    """count > 1,024: kp_layout's threads take 2 and 3 streams each and the threads past the end none
+    (2,049 streams: 683 threads of 3).  Forced, chunk 256, in_bytes exact: every stream's size, status
+    and place on the slow list are the oracle's, and every part was walked; in_bytes one short: the same
+    results by the wave route, no part walked."""
+    ins, want = many_streams(count)
+    assert _parts(ins, 256) == sum(0 if not b else (2 if len(b) > 16384 else 1) for b in ins) == count - count // 101 + count // 97
+    bad = {s for s in range(count) if want[s][1] != 0}
+    whole, comp, d_coff, nin = _upload(cuda, ins)
+    for hint in (nin, nin - 1):
+        sz, st, slow, last, chunk = _query(cuda, comp, d_coff, count, HINT[256], "p", hint)
+        assert chunk == 256
+        got = [(int(a), int(b)) for a, b in zip(sz, st)]
+        diff = [s for s in range(count) if got[s] != want[s]]
+        assert not diff, (hint, diff[:4], [got[s] for s in diff[:4]], [want[s] for s in diff[:4]])
+        assert slow == bad, (hint, sorted(slow)[:8], sorted(bad)[:8])
+        if hint == nin:
+            assert last[0] == _parts(ins, 256) and last[1] + last[2] <= last[0], last
+        else:
+            assert last == (0, 0, 0), last
+
+
 def test_chunk_1024_batch(cuda):
     """Streams of 2 to 5 parts of 64 KiB beside short and empty ones."""
     ins = [_long(70000, 347), b"", z._small_streams()[5], _long(300000, 349), HDR, _long(131072, 353), _long(131073, 359)]

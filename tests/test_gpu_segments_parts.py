@@ -165,6 +165,27 @@ def test_query_equals_host_walk_and_wave_route(cuda, dumped, max_len):
             assert list(seg_in[: count + 1]) == list(coff) and list(seg_out[: count + 1]) == list(ooff)
 
 
+@pytest.mark.parametrize("count", [1025, 2049])
+def test_layout_of_several_streams_per_thread(cuda, count):
+    """count > 1,024: kp_layout's threads take 2 and 3 streams each and the threads past the end none.
+    test_gpu_k2z_parts.many_streams (tiny streams of one part, every 97th of two parts, every 101st
+    empty; none holds a cut), forced, chunk 256, in_bytes exact: the arrays of the wave route, a segment
+    per stream, every part in the first pass; in_bytes one short: the same arrays, no part walked."""
+    from test_gpu_k2z_parts import many_streams
+
+    ins, _ = many_streams(count)
+    comp, d_coff, d_ooff, coff, ooff = _inputs(cuda, ins, [4 * len(b) + 16 for b in ins])
+    in_bytes = int(coff[-1] - coff[0])
+    wave, wlast = _query(cuda, comp, d_coff, d_ooff, count, count + 3, 0, 0, in_bytes, "v")
+    assert tuple(wave[3]) == (count, count) and wlast == (0, 0, 0, 0)
+    got, last = _query(cuda, comp, d_coff, d_ooff, count, count + 3, 0, 0, in_bytes, "p")
+    _same(got, wave, "parts against the wave route")
+    assert last[0] == sum(-(-len(b) // (64 * 256)) for b in ins) and last[1] + last[2] <= last[0], last
+    again, hlast = _query(cuda, comp, d_coff, d_ooff, count, count + 3, 0, 0, in_bytes - 1, "p")
+    _same(again, wave, "in_bytes one short")
+    assert hlast == (0, 0, 0, 0), hlast
+
+
 def _log_lines(rng, n):
     out = bytearray()
     while len(out) < n:

@@ -93,7 +93,8 @@ uint32_t emu_block(const uint8_t *in, uint32_t nb, uint32_t ps, uint32_t e, int3
     return wv.x[kZLanes - 1];
 }
 
-// ks_init, ks_first, ks_order and ks_fill over a batch; a stream without parts is the wave route's
+// kp_layout (the serial layout; its thread steps are tools/k2_layout_check.cpp's to check), ks_first,
+// ks_order and ks_fill over a batch; a stream without parts is the wave route's
 // (tools/k2_segs_check.hip holds that one to the same serial walk: here it is the serial walk itself)
 Walk serial(const Bytes &s, int64_t limit);
 template <int C>

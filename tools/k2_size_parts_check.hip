@@ -57,7 +57,8 @@ ez::KpRec emu_part(const uint8_t *in, uint32_t nb, uint32_t ps, bool known, uint
     return KpRec{acc.out, wv.a[0], wv.x[kZLanes - 1], acc.maxd, acc.fl};
 }
 
-// kp_init, kp_first and kp_order over a batch: the records are exactly as many as the layout says
+// kp_layout, kp_first and kp_order over a batch: the records are exactly as many as the layout says (the
+// layout here is the serial one; kp_layout's thread steps are tools/k2_layout_check.cpp's to check)
 template <int C>
 std::vector<Result> emulate(const std::vector<const Bytes *> &ins) {
     using namespace ez;
