@@ -1104,7 +1104,25 @@ def segments_last() -> tuple[int, int, int]:
     return int(c[0]), int(c[1]), int(c[2])
 
 
-def stream_breaks(comp, comp_off, block_size_limit: int = 0, max_len: int = 0, brk_cap: int | None = None, workspace=None, stream=None):
+def select_breaks_route(kind: str = "") -> None:
+    """Force the route of later stream_breaks calls ('p' the parts route at any stream length, given
+    in_bytes; 'v' never the parts route; '' = automatic).  Tests and A/B only."""
+    _check(_lib().ez_select_breaks_route(ord(kind) if kind else 0))
+
+
+def breaks_parts_last() -> tuple[int, int, int, int]:
+    """Of the last stream_breaks call, after its stream was synchronised: parts walked by the parts
+    route's first pass, parts taken as recorded, parts walked again, parts whose Break positions the
+    fill pass wrote (zeros: the route did not run, or found in_bytes too small)."""
+    c = (C.c_uint64 * 4)()
+    L = _lib()
+    L.ez_breaks_parts_last.argtypes = [C.POINTER(C.c_uint64)]
+    _check(L.ez_breaks_parts_last(c))
+    return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
+
+def stream_breaks(comp, comp_off, block_size_limit: int = 0, max_len: int = 0, brk_cap: int | None = None, workspace=None, stream=None,
+                  in_bytes: int = 0):
     """K2b: the Break positions of every stream comp[comp_off[s]:comp_off[s+1]] without decoding
     (Writer.WriteBreak's markers, which the batch decoders skip) -> (brk_idx, brk_pos, sizes, status),
     CUDA tensors.  Stream s owns brk_pos[brk_idx[s]:brk_idx[s+1]]: the bytes a Reader has produced at
@@ -1114,7 +1132,9 @@ def stream_breaks(comp, comp_off, block_size_limit: int = 0, max_len: int = 0, b
     them (brk_idx[-1], the number found, then exceeds brk_cap).  None: some room, and where it was too
     little the call reads the totals back (which waits for the stream) and asks again with enough.
     max_len is an optional host hint, the longest INPUT stream in bytes: it picks the chunk size and
-    nothing else.  workspace: ez_breaks_workspace(count) bytes (None: allocated here).  Asynchronous
+    nothing else.  in_bytes is an optional host hint, comp_off[-1] - comp_off[0] or more: with it the
+    parts route (a long stream's chain cut over many waves) can run; a wrong value costs speed, never
+    results.  workspace: ez_breaks_workspace(count) bytes (None: allocated here).  Asynchronous
     on the stream when brk_cap is given."""
     import torch
 
@@ -1128,7 +1148,7 @@ def stream_breaks(comp, comp_off, block_size_limit: int = 0, max_len: int = 0, b
     status = torch.empty(count, dtype=torch.int32, device=dev)
     brk_idx = torch.empty(count + 1, dtype=torch.int64, device=dev)
     brk_total = torch.empty(2, dtype=torch.int64, device=dev)
-    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, None, sizes.data_ptr(), status.data_ptr(), count, max_len, 0, 0)
+    b = _Batch(comp.data_ptr(), comp_off.data_ptr(), None, None, sizes.data_ptr(), status.data_ptr(), count, max_len, in_bytes, 0)
     cap = 4 * count + 64 if brk_cap is None else brk_cap
     while True:
         brk_pos = torch.empty(cap, dtype=torch.int64, device=dev)

@@ -792,7 +792,9 @@ inline Err DecompressBatchSegmented(int64_t block_size_limit, const ez_batch &b,
 // DecompressedSizeBatch reports; b.out and b.out_off are not used.  Device arrays: brk_idx[count+1],
 // brk_pos[brk_cap] (may be null with brk_cap == 0), brk_total[2], workspace of
 // ez_breaks_workspace(count) bytes (null: the exact decoder alone, the same results); b.max_len is the
-// longest INPUT stream (0: unknown).  Asynchronous on hip_stream.
+// longest INPUT stream (0: unknown); b.in_bytes is in_off[count] - in_off[0] or more (0: unknown; the
+// compressed buffer's length will do): with it the parts route, a long stream's chain cut over many
+// waves, can run, and any value gives the same arrays.  Asynchronous on hip_stream.
 inline Err StreamBreaksBatch(int64_t block_size_limit, const ez_batch &b, uint64_t *brk_idx, uint64_t *brk_pos, uint64_t brk_cap,
                              uint64_t *brk_total, void *workspace, void *hip_stream) {
     const int st = ez_stream_breaks_batch(block_size_limit, &b, brk_idx, brk_pos, brk_cap, brk_total, workspace, hip_stream);

@@ -425,14 +425,29 @@ extern "C" int ez_stream_breaks_batch(int64_t block_size_limit, const ez_batch *
     a.brk_pos = brk_pos;
     a.brk_cap = brk_cap;
     a.brk_total = brk_total;
+    a.in_bytes = b->in_bytes;  // the batch's input extent or more, if the caller knows it: the parts route needs it
     EZ_HIP(ez::launch_breaks(a, b->max_len, workspace, (hipStream_t)hip_stream));
+    return EZ_OK;
+}
+
+extern "C" int ez_select_breaks_route(int kind) {
+    if (kind != 0 && kind != 'p' && kind != 'v') return EZ_EINVAL;
+    ez::select_breaks_route(kind);
+    return EZ_OK;
+}
+
+extern "C" int ez_breaks_parts_last(uint64_t counts[4]) {
+    if (!counts) return EZ_EINVAL;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (device_count() <= 0) return EZ_EDEVICE;
+    EZ_HIP(ez::breaks_parts_last(counts));
     return EZ_OK;
 }
 
 // Frees the device scratch the batch calls keep between calls (no reference counterpart; like a
 // caching allocator's empty_cache): the K1 / K1c scratch and K2j workspaces per (device, HIP stream),
 // the multi-device calls' pooled shard buffers, the Reader handles' shared K2j workspace,
-// ez_writer_write_many's staging, ez_decompress_batch_segmented's scratch and the segment query's parts-route scratch, on `device` (< 0: every device).  Scratch a call is using at that moment is kept.
+// ez_writer_write_many's staging, ez_decompress_batch_segmented's scratch, the segment query's and the Break index's parts-route scratch, on `device` (< 0: every device).  Scratch a call is using at that moment is kept.
 extern "C" int ez_release_cached(int device) {
     const int have = device_count();
     if (have <= 0) return EZ_EDEVICE;
@@ -445,6 +460,7 @@ extern "C" int ez_release_cached(int device) {
         ez::size_cache().trim(d);
         ez::segs_cache().trim(d);
         ez::segs_parts_cache().trim(d);
+        ez::breaks_parts_cache().trim(d);
         reader_release_cached(d);
         writer_release_cached(d);
     }
@@ -453,7 +469,7 @@ extern "C" int ez_release_cached(int device) {
 }
 
 // Testing: sets the scratch ez_release_cached would free to `byte` (0..255; -1: touches nothing) and
-// reports its size in *bytes (may be NULL): the K1 / K1c scratch, K2j workspaces, both parts routes' and
+// reports its size in *bytes (may be NULL): the K1 / K1c scratch, K2j workspaces, the three parts routes' and
 // ez_decompress_batch_segmented's scratch per (device, HIP stream), ez_writer_write_many's staging
 // (device and pinned), the Reader handles' shared K2j workspace and the multi-device calls' pooled
 // shard buffers, on `device` (< 0: every device).  Scratch a call is using at that moment is skipped.
@@ -473,6 +489,7 @@ extern "C" int ez_fill_cached(int device, int byte, uint64_t *bytes) {
         ok &= ez::size_cache().fill(d, byte, &n);
         ok &= ez::segs_cache().fill(d, byte, &n);
         ok &= ez::segs_parts_cache().fill(d, byte, &n);
+        ok &= ez::breaks_parts_cache().fill(d, byte, &n);
         ok &= reader_fill_cached(d, byte, &n);
         ok &= writer_fill_cached(d, byte, &n);
         ok &= multi_fill_cached(d, byte, &n);

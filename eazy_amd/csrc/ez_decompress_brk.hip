@@ -32,12 +32,17 @@
 //   exact fill   the exact decoder over the list once more, for the listed streams that own Breaks.
 // Without a workspace the two exact stages run over the whole batch.  A stream without Breaks is
 // walked once.
+// The parts route (ez_decompress_brk_parts.hip) takes the streams that have parts where
+// breaks_parts_route picks it and the caller gave in_bytes: its layout, first and order passes go in
+// front of the count stage and its fill pass in front of the fill stage; k2b_walk, with the route's gate
+// and part bases in its arguments, then walks only the streams without parts (all of them where the
+// gate stayed closed).
 #include <hip/hip_runtime.h>
 
 #include "ez_bytes.h"
+#include "ez_cache.h"
 #include "ez_internal.h"
-#include "ez_k2_brk.h"
-#include "ez_k2_walk.h"
+#include "ez_k2_brk_walk.h"
 
 namespace ez {
 namespace {
@@ -52,56 +57,12 @@ struct KbEnd {
 template <int C, bool FILL, class Put>
 __device__ __forceinline__ KbEnd kb_stream(uint8_t *stage, uint32_t (*bm)[C / 32 + 1], const uint8_t *b, uint32_t nb, int32_t lim32,
                                            int64_t limit, Put put) {
-    const int lane = lane_id();
-    const auto none = [](uint32_t, uint64_t) {};
-    const auto put0 = [&](uint32_t k, uint64_t out) {
-        if (FILL && lane == 0) put(k, out);
-    };
     KbState st = kb_start();
     uint32_t sb = 0;
     while (!st.stop && sb < nb) {
-        const KzWalk k = kz_walk<C>(stage, bm, b, nb, sb, sb, true, sb);
-        if (!k.settled) {
-            st.stop = true;
-            break;
-        }
-        const KzWin w{stage, sb};
-        const KbSum r = kb_sum<C>(w, sb, lane, nb, k.a, k.x, lim32, limit, none);
-        const uint64_t io = wscan_add_u64(r.out);
-        const uint32_t ib = (uint32_t)wscan_add((int32_t)r.nbrk);  // (a super-block holds at most 32 x C Breaks)
-        uint64_t ev = wballot(r.fl != 0);
-        uint64_t base = 0;   // the prefixes taken into the state so far
-        uint32_t bbase = 0;
-        int from = 0;        // the first lane whose sums are not in the state yet
-        // the lanes from .. to store their Breaks before their events: the state holds everything before lane `from`
-        auto fill = [&](int to) {
-            if (!FILL || !(lane >= from && lane <= to && r.nbrk != 0)) return;
-            const uint64_t ob = st.total + (io - r.out - base);
-            const uint32_t bb = st.nbrk + (ib - r.nbrk - bbase);
-            (void)kb_sum<C>(w, sb, lane, nb, k.a, k.x, lim32, limit, [&](uint32_t i, uint64_t out) { put(bb + i, ob + out); });
-        };
-        while (ev) {
-            const int j = ffs64(ev);
-            ev &= ev - 1;
-            fill(j);
-            // the lanes before j, and lane j's tokens before its event
-            const uint64_t ioj = __shfl(io, j, kWave);
-            const uint32_t ibj = (uint32_t)__shfl((int)ib, j, kWave);
-            st.total += ioj - base;
-            base = ioj;
-            st.nbrk += ibj - bbase;
-            bbase = ibj;
-            st.maxd = max(st.maxd, wmax_u32(lane >= from && lane <= j ? r.maxd : 0u));
-            from = j + 1;
-            kb_walk<C>(w, sb, j, nb, (uint32_t)__shfl((int)r.epos, j, kWave), (uint32_t)__shfl((int)k.x, j, kWave), lim32, limit, st, put0);
-            if (st.stop) break;
-        }
+        const uint32_t x = kb_block<C, FILL>(stage, bm, b, nb, sb, sb, sb, lim32, limit, st, put);
         if (st.stop) break;
-        fill(kWave - 1);
-        st.total += __shfl(io, kWave - 1, kWave) - base;
-        st.nbrk += (uint32_t)__shfl((int)ib, kWave - 1, kWave) - bbase;
-        st.maxd = max(st.maxd, wmax_u32(lane >= from ? r.maxd : 0u));
-        sb = __shfl(k.x, kWave - 1, kWave);
+        sb = x;
     }
     return KbEnd{st, sb};
 }
@@ -116,7 +77,9 @@ __global__ __launch_bounds__(64) void k2b_walk(BrkArgs A) {
     const int lane = lane_id();
     const int64_t limit = A.block_size_limit;
     const int32_t lim32 = k2_lim32(limit);
+    const bool parted = A.parts_gate && *A.parts_gate;  // (the parts route walks the streams that have parts)
     for (uint64_t s = blockIdx.x; s < A.count; s += gridDim.x) {
+        if (parted && A.parts_base[s] != A.parts_base[s + 1]) continue;
         uint64_t g0 = 0, n = 0;
         if (FILL) {
             g0 = A.brk_idx[s];
@@ -188,6 +151,14 @@ uint64_t breaks_workspace_bytes(uint64_t count) { return (64 + count * 8 + 15) &
 hipError_t launch_breaks(const BrkArgs &a0, uint64_t max_len, void *workspace, hipStream_t st) {
     BrkArgs a = a0;
     hipError_t e;
+    a.parts_gate = a.parts_base = nullptr;
+    // The parts route needs the batch's extent to size its records without a read-back (the caller's
+    // in_bytes hint) and the workspace's list for the streams it hands over.
+    int pchunk = workspace ? breaks_parts_route(max_len, a.count, a.in_bytes) : 0;
+    breaks_parts_none();  // (until the route's scratch is leased: the last query did not take it)
+    CacheLease please;    // (held until the last launch)
+    void *pws = nullptr;
+    uint64_t pws_cap = 0;
     if (a.count != 0) {
         const int chunk = size_chunk(max_len);
         // every wave of the chip busy at most (32 per CU); the streams beyond go round the grid
@@ -205,6 +176,15 @@ hipError_t launch_breaks(const BrkArgs &a0, uint64_t max_len, void *workspace, h
             a.handed = (uint32_t *)workspace + 16 + a.count;
             d.slow = a.list;
             if ((e = hipMemsetAsync(workspace, 0, 64, st)) != hipSuccess) return e;
+            if (pchunk) {
+                e = launch_breaks_parts(a, pchunk, st, please, &pws, &pws_cap);
+                if (e == hipErrorOutOfMemory) {  // (no scratch: the wave route)
+                    pchunk = 0;
+                    a.parts_gate = a.parts_base = nullptr;
+                } else if (e != hipSuccess) {
+                    return e;
+                }
+            }
             if (chunk == 64) hipLaunchKernelGGL((k2b_walk<64, false>), dim3(grid), dim3(64), 0, st, a);
             else if (chunk == 1024) hipLaunchKernelGGL((k2b_walk<1024, false>), dim3(grid), dim3(64), 0, st, a);
             else hipLaunchKernelGGL((k2b_walk<256, false>), dim3(grid), dim3(64), 0, st, a);
@@ -215,6 +195,7 @@ hipError_t launch_breaks(const BrkArgs &a0, uint64_t max_len, void *workspace, h
         hipLaunchKernelGGL(k2b_scan, dim3(1), dim3(kScanThreads), 0, st, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (workspace) {
+            if (pchunk && (e = launch_breaks_parts_fill(a, pchunk, pws, pws_cap, st)) != hipSuccess) return e;
             if (chunk == 64) hipLaunchKernelGGL((k2b_walk<64, true>), dim3(grid), dim3(64), 0, st, a);
             else if (chunk == 1024) hipLaunchKernelGGL((k2b_walk<1024, true>), dim3(grid), dim3(64), 0, st, a);
             else hipLaunchKernelGGL((k2b_walk<256, true>), dim3(grid), dim3(64), 0, st, a);

@@ -357,8 +357,29 @@ struct BrkArgs {
     uint64_t *brk_total;      // 2
     uint32_t *list;           // the workspace's hand-over list, [0] = its length, and the per-stream
     uint32_t *handed;         // "handed over" words (set by the launcher)
+    // the parts route (ez_decompress_brk_parts.hip), optional: in_bytes, the caller's hint of in_off[count]
+    // - in_off[0] (0 = unknown: the wave route).  parts_gate, parts_base (set by the launcher): k2b_walk
+    // walks the whole batch where the device word parts_gate is 0 (the hint was too small), else only
+    // the streams s without parts (parts_base[s] == parts_base[s + 1])
+    uint64_t in_bytes;
+    const uint32_t *parts_gate;
+    const uint32_t *parts_base;
 };
 uint64_t breaks_workspace_bytes(uint64_t count);
+// K2b's parts route: a long stream's chain cut over many waves, chunk 256 or 1,024; needs a.in_bytes and
+// the workspace (a.list, a.handed).  launch_breaks_parts: layout, first and order passes (out_size,
+// status, brk_idx[s] = the Breaks, handed[s] or the list for the streams with parts; the parts' entry
+// states); sets a's parts_gate / parts_base for k2b_walk behind it, and *pws for launch_breaks_parts_fill,
+// which goes behind k2b_scan.  lease: the scratch, held until the last launch.
+// (hipErrorOutOfMemory: the scratch could not be had, nothing was launched)
+int breaks_parts_route(uint64_t max_len, uint64_t count, uint64_t in_bytes);  // its chunk for a batch; 0: the wave route
+hipError_t launch_breaks_parts(BrkArgs &a, int chunk, hipStream_t s, CacheLease &lease, void **pws, uint64_t *pws_cap);
+hipError_t launch_breaks_parts_fill(const BrkArgs &a, int chunk, void *pws, uint64_t pws_cap, hipStream_t s);
+DevCache &breaks_parts_cache();
+void select_breaks_route(int v);  // 0 = automatic, 'p' parts at any length, 'v' the wave route (tests, A/B)
+int selected_breaks_route();
+void breaks_parts_none();         // the last query did not take the parts route
+hipError_t breaks_parts_last(uint64_t counts[4]);  // parts in the first pass, taken as recorded, walked again, filled
 // max_len: the caller's hint, the longest input stream (0 = unknown), which picks the chunk (size_chunk);
 // workspace null: the exact decoder alone
 hipError_t launch_breaks(const BrkArgs &a, uint64_t max_len, void *workspace, hipStream_t s);

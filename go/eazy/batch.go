@@ -470,6 +470,7 @@ func StreamBreaksBatch(streams [][]byte, blockSizeLimit int) (breaks [][]uint64,
 	b := C.ez_batch{
 		in: (*C.uint8_t)(dIn), in_off: (*C.uint64_t)(dInOff), out_size: (*C.uint64_t)(dSize), status: (*C.int32_t)(dStatus),
 		count: C.uint64_t(count), max_len: C.uint64_t(maxLen),
+		in_bytes: C.uint64_t(inOff[count]), // (the query's parts route needs the extent)
 	}
 	room := uint64(4*count + 64)
 	var total [2]uint64

@@ -444,21 +444,50 @@ int ez_segments_last(uint64_t counts[3]);
  * ez_decompressed_size_batch reports.
  * Uses b->in, in_off, out_size (required), status (may be NULL), count and max_len (host hint: the
  * longest INPUT stream in bytes, 0 = unknown; it picks the chunk size as ez_decompressed_size_chunk
- * says and nothing else: any value gives the same arrays); out, out_off, in_bytes and out_bytes are
+ * says and nothing else: any value gives the same arrays) and in_bytes (host hint: in_off[count] -
+ * in_off[0] or more, 0 = unknown; it enables the parts route below and nothing else: any value gives
+ * the same arrays); out, out_off and out_bytes are
  * ignored.  workspace >= ez_breaks_workspace(count) device bytes enables the fast walk (a wave per
  * stream over the true token chain, once to count and, for the streams that own Breaks, once more to
  * write; streams it cannot take go whole to the exact decoder run dry); NULL = the exact decoder alone,
  * with the same results.  The workspace's contents on entry are ignored and nothing is written past
- * its size.  All pointers are device pointers.  Asynchronous on hip_stream; never waits for the stream.
+ * its size.
+ * The parts route, for the few long streams that one wave each would bound: every stream's chain cut
+ * on K2z's fixed grid of parts of 64 chunks; a wave per part writes K2g's state-independent record and
+ * the part's Breaks; a wave per stream follows the true chain through the records, walks again only
+ * the parts it enters elsewhere or that are marked, leaves every part's entry state and the stream's
+ * verdict (all or nothing: a stream it cannot take goes whole to the exact decoder); a wave per part
+ * whose chain holds a Break then writes that part's positions in place.  The route sizes its scratch
+ * from in_bytes, so it runs only where the caller gives in_bytes and a workspace (and the route is
+ * selected, see ez_select_breaks_route); a kernel checks the real extent against the hint before
+ * anything indexes the scratch, and an under-stated hint leaves the whole batch to the wave route (an
+ * over-stated one only enlarges the scratch, which is the library's own, kept per (device, HIP
+ * stream) and freed by ez_release_cached; if it cannot be had the call takes the wave route).
+ * All pointers are device pointers.  Asynchronous on hip_stream; never waits for the stream.
  * Memory touched: reads in[0 .. in_off[count]) as ez_decompress_batch does; writes only
  * out_size[0..count), status[0..count), brk_idx[0..count], brk_pos[0..brk_total[0]), brk_total[0..1]
  * and the workspace.  EZ_EINVAL for a NULL b, out_size, brk_idx or brk_total, and for a NULL brk_pos
  * with brk_cap != 0; count == 0 writes brk_idx[0] = 0 and brk_total = {0, 0} and returns EZ_OK.
  * Held by tests/test_k2_breaks.py, tests/test_capi_breaks.py, tests/test_gpu_breaks.py,
- * tests/test_cpp_breaks.py and (offsets past 2^31 and 2^32) tests/test_gpu_high_offsets.py. */
+ * tests/test_cpp_breaks.py, tests/test_k2_brk_parts.py, tests/test_gpu_breaks_parts.py and (offsets
+ * past 2^31 and 2^32) tests/test_gpu_high_offsets.py. */
 size_t ez_breaks_workspace(uint64_t count);
 int ez_stream_breaks_batch(int64_t block_size_limit, const ez_batch *b, uint64_t *brk_idx, uint64_t *brk_pos, uint64_t brk_cap,
                            uint64_t *brk_total, void *workspace, void *hip_stream);
+/* Testing / A-B measurement: the route of later ez_stream_breaks_batch calls in this process: 'p' the
+ * parts route at any stream length (it still needs b->in_bytes and a workspace; chunk 1,024 where the
+ * wave route takes 1,024, else 256), 'v' never the parts route, 0 = automatic (today: the wave route).
+ * EZ_EINVAL for any other value.  Not thread-safe against concurrent calls.
+ * Host function: touches no device memory. */
+int ez_select_breaks_route(int kind);
+/* Introspection (tests, measurement): of the last ez_stream_breaks_batch call of this process,
+ * counts[0] = parts the parts route walked in its first pass, counts[1] = parts whose record the true
+ * chain took as it stood, counts[2] = parts walked again from the true state (parts a token spans are
+ * in neither), counts[3] = parts whose Break positions the fill pass wrote; all 0 where the parts route
+ * did not run or found in_bytes too small.  The caller has synchronised that call's stream.  Memory
+ * touched: the call reads 64 bytes of the library's own scratch back from the device and writes
+ * counts[0 .. 3]; EZ_EINVAL for NULL. */
+int ez_breaks_parts_last(uint64_t counts[4]);
 
 /* ---- host-memory batches over several devices (SURVEY §8b device_or_all) ----
  * Streams share no state (writer.go:40-45, reader.go:17-40), so a batch splits into contiguous
@@ -506,7 +535,7 @@ int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in
 /* Frees the device scratch kept between batch calls (no reference counterpart; a caching
  * allocator's empty_cache).  The set: per (device, HIP stream), the K1 / K1c / K1x scratch of
  * ez_compress_batch and _writes, the K2j workspaces of ez_decompress_batch, the parts routes' scratch
- * of ez_decompressed_size_batch and ez_stream_segments_batch, ez_decompress_batch_segmented's scratch and ez_writer_write_many's
+ * of ez_decompressed_size_batch, ez_stream_segments_batch and ez_stream_breaks_batch, ez_decompress_batch_segmented's scratch and ez_writer_write_many's
  * staging (device and pinned); per device, the Reader handles' shared K2j workspace; and the
  * multi-device calls' pooled shard buffers.  device < 0 = every device.  Scratch in use by a
  * concurrent call is kept.  Entries beyond 8 streams per device are also freed least recently used
@@ -516,7 +545,7 @@ int ez_decompressed_size_batch_multi(int64_t block_size_limit, const uint8_t *in
  * and tests/test_gpu_call_order.py). */
 int ez_release_cached(int device);
 /* Testing / introspection: sets every idle buffer of the set ez_release_cached frees (the same
- * set: the per-(device, HIP stream) scratch of K1 / K1c / K1x, K2j, both parts routes,
+ * set: the per-(device, HIP stream) scratch of K1 / K1c / K1x, K2j, the three parts routes,
  * ez_decompress_batch_segmented and ez_writer_write_many, device and pinned; the Reader handles'
  * shared K2j workspace; the multi-device calls' pooled shard buffers) to `byte` (0..255), or touches
  * nothing and only counts with byte = -1; *bytes (may be NULL) gets the device and pinned bytes
